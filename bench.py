@@ -7,7 +7,11 @@ V=10000, T=27 caption slots; random-init weights (no checkpoints offline).
 One step = encoder fwd + decoder fwd + fused loss + decoder bwd + RCCL grad
 all-reduce (N>1) + Adam, inputs resident in HBM before the timed region.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+      A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything
+      else after the timed region: the in-step kernel timestamps and rooflines, the fp32 leg, the CPU baseline
+      (each still has its own --no-... / --fp32-steps switch).  --dump-outputs DIR writes what the last timed
+      step computed as DIR/<name>.npy (float32; seeded samples of the large arrays).
       N > 1: this process starts the N rank processes itself (torch.distributed.run, one rank per GPU, before
       anything touches a GPU) and exits with their status; launched by torch.distributed.run directly it is one
       of the ranks (WORLD_SIZE set) and checks that WORLD_SIZE == --gpus.
@@ -43,7 +47,14 @@ def parse():
                     help="cfg4: no teacher forcing (greedy argmax feedback inside the time loop, decoder.py:131-133)")
     ap.add_argument("--bert", action="store_true",
                     help="cfg5: frozen BERT word embeddings (V=30522, E=768, T=32), simple deep output (--ado off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the diagnostic phases (in-step kernel timestamps, per-kernel "
+                         "rooflines), the fp32 leg and the CPU baseline; a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, logits, alphas, encoder "
+                         "features, the updated decoder parameters and their gradients) as DIR/<name>.npy, float32, "
+                         "large arrays as a fixed seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=8,
                     help="images per step of the bounded CPU-baseline sample (the reference's cfg1 batch)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
@@ -614,6 +625,26 @@ def fp32_step(args, enc, dec, imgs, caps, pad_id, skip_ids, world):
             "note": "exact-parity path (fp32 MFMA), eager, rank 0 only; not the headline value"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all arrays together (float32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of ``arrays`` (name -> tensor) as path/<name>.npy, float32, flattened.  The
+    budget is shared evenly: an array with more elements than its share is written as a sample at fixed indices
+    (drawn with replacement from a generator seeded by the array's name, so two builds of the project write
+    the same elements)."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        v = t.detach().reshape(-1)
+        if v.numel() > cap:
+            idx = torch.randint(0, v.numel(), (cap,), generator=torch.Generator().manual_seed(zlib.crc32(name.encode())))
+            v = v[idx.to(v.device)]
+        np.save(os.path.join(path, name + ".npy"), v.float().cpu().numpy())
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -663,6 +694,10 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world} ranks were launched")
     dp = world > 1 or args.dp_rehearse   # the data-parallel path (process group, bucket all-reduces)
+    # everything beside the headline figure runs after the timed region, and only with --full
+    diagnostics = args.full and not args.no_diagnostics
+    fp32_steps = args.fp32_steps if args.full else 0
+    with_cpu_baseline = args.full and not args.no_cpu_baseline
     if args.dp_rehearse and world == 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", str(free_port()))
@@ -725,12 +760,16 @@ def main():
     caps = synthetic_captions(B, args.seq, args.vocab, generator=g, bert=args.bert, device=dev)
     torch.cuda.synchronize()
 
+    last = {} if args.dump_outputs else None   # --dump-outputs: the eager step's latest features / preds / alphas
+
     def fwd_bwd():
         with torch.no_grad():
             feats = enc(imgs)
         preds, alphas = dec(feats, caps)
         loss, metrics = sat_amd.caption_loss(preds, alphas, caps, pad_id=pad_id, skip_ids=skip_ids)
         loss.backward()
+        if last is not None:
+            last.update(features=feats, preds=preds, alphas=alphas)
         return loss
 
     # eager DP: bucket all-reduces launched from inside the decoder's backward (phase hooks)
@@ -762,7 +801,7 @@ def main():
         of batch i, its all-reduce and Adam run on the main stream (the encoder reads no decoder parameter).
         stamped: every conv launch and every per-step decoder launch writes in-kernel timestamps (the diagnostic
         copies captured after the timed region; the timed graphs carry no stamp pointers at all)."""
-        G = dict(enc=[], dec=[], rec=[], feats=[], loss=[], stamps_enc=[], stamps_dec=[])
+        G = dict(enc=[], dec=[], rec=[], feats=[], loss=[], outs=[], stamps_enc=[], stamps_dec=[])
         one = torch.ones((), device=dev)
         for k in range(nbuf):
             if stamped:
@@ -792,6 +831,8 @@ def main():
             G["dec"].append(gd)
             G["rec"].append(gr)
             G["loss"].append(loss_k)
+            if args.dump_outputs:   # the replays' preds / alphas stay readable after the timed steps
+                G["outs"].append((preds, alphas))
             dec.policy = policy
         dec.defer_recurrent_backward(False)
         torch.cuda.synchronize()
@@ -883,9 +924,24 @@ def main():
     loss_v = loss.item()
     enc_ms = sum(s.elapsed_time(e) for s, e in enc_events) if use_graph else None
     dec_ms = sum(s.elapsed_time(e) for s, e in dec_events) if use_graph and dec_events else None
+    if args.dump_outputs and rank == 0:
+        # the last timed step: its graph set's outputs (the last replay of buffer (steps - 1) % nbuf), the
+        # gradients it left and the parameters after its Adam update -- before any diagnostic phase steps further
+        if use_graph:
+            k = (args.steps - 1) % nbuf
+            outs = dict(features=G["feats"][k], preds=G["outs"][k][0], alphas=G["outs"][k][1])
+        else:
+            outs = dict(last)
+        arrays = dict(loss=loss, **outs)
+        for n, p in dec.named_parameters():
+            arrays[f"param.{n}"] = p
+            if p.grad is not None:
+                arrays[f"grad.{n}"] = p.grad
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays, outs   # the diagnostic phase releases the timed graphs' pools
     diag_phase = None
     stamps_enc, stamps_dec = [], []
-    if use_graph and not args.no_diagnostics and not args.no_step_stamps:
+    if use_graph and diagnostics and not args.no_step_stamps:
         # diagnostic phase (every rank: the all-reduces are collective): stamped copies of the graphs, captured
         # now (the timed graphs are released first), run in the same overlapped schedule with the timestamps on
         loss = None
@@ -904,7 +960,7 @@ def main():
         diag_phase = {"steps": n_diag, "ms_per_step": round(1000 * (time.perf_counter() - t1) / n_diag, 3)}
         for st in stamps_enc + stamps_dec:
             st.enable(False)
-    diag = rank == 0 and not args.no_diagnostics
+    diag = rank == 0 and diagnostics
 
     def collect(intervals=False):
         conv = instep_conv_durations(stamps_enc, launches, intervals=intervals) if stamps_enc else None
@@ -954,7 +1010,7 @@ def main():
         step_kernels["step_chain"] = dict(alone=chain_alone, overlapped=chain_overlapped,
                                           note="per time step: first-kernel start to the next step's first-kernel "
                                                "start (interval) beside the sum of the step's kernel spans")
-    fp32_leg = fp32_step(args, enc, dec, imgs, caps, pad_id, skip_ids, world) if world == 1 and args.fp32_steps > 0 \
+    fp32_leg = fp32_step(args, enc, dec, imgs, caps, pad_id, skip_ids, world) if world == 1 and fp32_steps > 0 \
         else None
     if roof is not None:
         roof["traffic"], roof["traffic_source"] = pmc_traffic(args.network, roof["cls"])
@@ -1005,7 +1061,7 @@ def main():
         }
         if fp32_leg is not None:
             out["fp32"] = fp32_leg
-        if not args.no_cpu_baseline and world == 1:
+        if with_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if dp:

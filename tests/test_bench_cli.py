@@ -89,6 +89,32 @@ def test_bench_defaults_time_enough_steps(monkeypatch):
     assert a.steps >= 200 and a.fp32_steps > 0
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full (diagnostic phases, fp32 leg, CPU baseline) and --dump-outputs are off unless asked for."""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = _parse(monkeypatch, "--full", "--dump-outputs", "out")
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_seeded_float32_samples(tmp_path, monkeypatch):
+    """Small arrays whole, large ones as the same seeded sample on every call, float32, inside the budget."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 3 * 100)   # 100 elements per array
+    big = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    arrays = {"loss": torch.tensor(1.5), "small": torch.arange(6, dtype=torch.bfloat16).reshape(2, 3), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), dict(reversed(list(arrays.items()))))
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].tolist() == [1.5] and a["small"].tolist() == [0, 1, 2, 3, 4, 5]
+    assert a["big"].shape == (100,) and len(set(a["big"].tolist())) > 50
+    assert set(a["big"].tolist()) <= set(range(1000))
+    for n in arrays:   # the sample depends on the array's name and size only
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy"))
+    assert sum(v.nbytes for v in a.values()) <= 4 * 3 * 100
+
+
 def test_gpus_flag_relaunches_as_ranks(monkeypatch):
     """`python bench.py --gpus N` (N > 1, not already a rank) starts N ranks through torch.distributed.run with the
     same arguments, on 127.0.0.1, and exits with their status; the parent touches no GPU."""

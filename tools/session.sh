@@ -47,7 +47,7 @@ d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print(d["value"], d["ms_per_step"])
 PY
 }
-QUIET="--no-cpu-baseline --fp32-steps 0"
+QUIET="--full --no-cpu-baseline --fp32-steps 0"   # the diagnostics stay on unless --no-diagnostics follows
 n=0
 for s in "$@"; do
   n=$((n + 1))
@@ -62,12 +62,12 @@ for s in "$@"; do
                --timeout-method thread -k "${s#testsv:}"
            rc=$?; grep -E "^FAILED|gradient errors" "$OUT/testsv_$n.log" | head -40; [ $rc -le 1 ] || exit $rc ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 400 python bench.py || exit $? ;;
+    bench) run bench 400 python bench.py --full || exit $? ;;
     bench64) run bench64 300 python bench.py --batch 64 $QUIET || exit $? ;;
     benchq) run benchq 300 python bench.py --steps 100 $QUIET || exit $? ;;
     cfg4) run cfg4 300 python bench.py --no-tf $QUIET || exit $? ;;
     dpr)   # the data-parallel path of bench.py over a one-rank RCCL process group (--dp-rehearse)
-      run dpr 300 python bench.py --dp-rehearse --steps 30 --no-cpu-baseline --fp32-steps 0 || exit $? ;;
+      run dpr 300 python bench.py --dp-rehearse --steps 30 $QUIET || exit $? ;;
     gloo2) # the N > 1 path rehearsed on one GPU: two ranks over gloo at cfg3's per-rank batch (64)
            # (bench.py --gpus 2 starts the two ranks itself, as the driver's `bench.py --gpus N` does)
            run gloo2 400 python bench.py --gpus 2 --batch 64 --dist-backend gloo --steps 30 $QUIET || exit $? ;;
@@ -77,7 +77,7 @@ for s in "$@"; do
               python bench.py --steps 100 $QUIET --no-diagnostics ${args//,/ } || exit $?
           python tools/prof_summary.py "$OUT/prof_$label" "$OUT/prof_$label.log" "$OUT/prof_$label.json" | head -40 ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-              python bench.py || exit $?
+              python bench.py --full || exit $?
           python tools/prof_summary.py "$OUT/prof" "$OUT/prof.log" "$OUT/prof_summary.json" | head -60 ;;
     pmcdec)
       for c in FETCH_SIZE WRITE_SIZE; do
