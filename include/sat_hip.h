@@ -279,6 +279,29 @@ int sat_decoder_beam_search(const SatDecoderDims* d, const SatDecoderLayout* lay
                             void* workspace, size_t workspace_bytes, int32_t* out_ids, int* out_len,
                             float* out_alphas, int* out_alpha_rows, float* out_score, void* stream);
 
+/* --- batched beam search: n_images images x beam_size beams decoded together --------------------------
+ * Per image exactly sat_decoder_beam_search's result (same candidate order, end ids, winner rule and
+ * no-completion case), but every launch carries n_images * beam_size rows and the top-k selection,
+ * end-token retirement, survivor reordering, histories and the final backtrack all run on the device.
+ * img_features: DEVICE [n_images, L, D], one row block per image, NOT expanded to beam rows.
+ * The step loop issues no copy and no synchronise except a 4-byte early-exit poll every 8th step; one
+ * synchronise follows the final copies, so `stream` is idle on return (NOT capturable).
+ * Results are written to HOST memory, image n at:
+ *   out_ids        + n * (max_step + 2)        sentence incl. the start token, out_len[n] ids
+ *   out_alphas     + n * (max_step + 2) * L    out_alpha_rows[n] alpha rows (first row = ones)
+ *   out_score[n]                               summed raw logits; -inf when no beam of the image completed:
+ *                                              then ids = [0], len = 1 and the alpha rows are the last
+ *                                              step's live rows.
+ * Requires n_images >= 1, 1 <= beam_size <= min(64, max_step + 2), n_images * beam_size <= 1024 and the
+ * dims sat_decoder_beam_search accepts; otherwise SAT_ERR_INVALID / 0 bytes.  The workspace holds the
+ * alpha history: (max_step + 1) * n_images * beam_size * L floats on top of the per-row step buffers. */
+size_t sat_decoder_beam_batch_workspace_bytes(const SatDecoderDims* d, int n_images, int beam_size, int max_step);
+int sat_decoder_beam_search_batch(const SatDecoderDims* d, const SatDecoderLayout* lay, const float* params,
+                                  const void* params_lp, const void* img_features, int n_images, int beam_size,
+                                  int max_step, void* workspace, size_t workspace_bytes, int32_t* out_ids,
+                                  int* out_len, float* out_alphas, int* out_alpha_rows, float* out_score,
+                                  void* stream);
+
 /* --- loss + metrics (train.py:135-162, utils.py:44-80,101-107) ----------- */
 size_t sat_caption_loss_workspace_bytes(int B, int T, int L);
 /* out[0]=loss, [1]=CE, [2]=att-reg, [3]=#top1-correct, [4]=#top5-correct, [5]=#non-pad targets,

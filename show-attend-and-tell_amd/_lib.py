@@ -119,6 +119,10 @@ _SIGNATURES = [
     ("sat_decoder_beam_search", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout), c_void_p,
                                         c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("sat_decoder_beam_batch_workspace_bytes", c_size_t, [ctypes.POINTER(SatDecoderDims), c_int, c_int, c_int]),
+    ("sat_decoder_beam_search_batch", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout),
+                                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("sat_caption_loss_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
     ("sat_caption_loss_forward", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -370,6 +370,61 @@ class Decoder(nn.Module):
             return [0], torch.from_numpy(alpha.copy())
         return ids[:n_ids.value].tolist(), alpha.tolist()
 
+    def caption_batch(self, img_features, beam_size, max_step=50, max_images=64):
+        """Beam search for N images at once (sat_decoder_beam_search_batch): every launch carries
+        ``N * beam_size`` rows and the beam bookkeeping stays on the device.
+
+        ``img_features`` [N, L, D] (fp32 or bf16, one row block per image, NOT expanded to beam rows).
+        Returns a list of N ``(sentence, alphas, score)``; ``sentence`` / ``alphas`` are what
+        ``caption`` returns for that image alone (``[0]`` and the last step's alpha rows, with the
+        reference's notice printed once per such image, when none of its beams completed) and
+        ``score`` the winner's summed logits (``-inf`` then).  N is decoded in chunks of at most
+        ``max_images`` images."""
+        import numpy as np
+        L.require_device(img_features)
+        if img_features.dim() != 3:
+            raise ValueError(f"img_features must be [N, L, D], got {tuple(img_features.shape)}")
+        beam_size, max_step, max_images = int(beam_size), int(max_step), int(max_images)
+        if max_images < 1:
+            raise ValueError("max_images must be >= 1")
+        feats_all = img_features.contiguous()
+        self._ensure_flat(feats_all.device)
+        if feats_all.dtype == torch.bfloat16:
+            self._ensure_lp()
+        lay = self._layout()
+        lib = L.lib()
+        out = []
+        for lo in range(0, feats_all.shape[0], max_images):
+            feats = feats_all[lo:lo + max_images]
+            n = feats.shape[0]
+            dims = self._dims(feats, torch.empty(1, 3, dtype=torch.long))
+            dims.training = 0
+            ws_bytes = lib.sat_decoder_beam_batch_workspace_bytes(ctypes.byref(dims), n, beam_size, max_step)
+            if ws_bytes == 0:
+                raise RuntimeError("sat_amd.Decoder.caption_batch: unsupported shape / beam size (1..64, at most "
+                                   "max_step + 2) / images * beam_size > 1024")
+            ws = torch.empty(ws_bytes, device=feats.device, dtype=torch.uint8)
+            cap = max_step + 2
+            ids = np.zeros((n, cap), dtype=np.int32)
+            alphas = np.zeros((n, cap, dims.L), dtype=np.float32)
+            n_ids, n_rows = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+            score = np.zeros(n, dtype=np.float32)
+            lp = self._flat_lp if dims.dtype == L.SAT_BF16 else None
+            L.check(lib.sat_decoder_beam_search_batch(ctypes.byref(dims), ctypes.byref(lay), L.ptr(self._flat),
+                                                      L.ptr(lp), L.ptr(feats), n, beam_size, max_step, L.ptr(ws),
+                                                      ws_bytes, ids.ctypes.data, n_ids.ctypes.data,
+                                                      alphas.ctypes.data, n_rows.ctypes.data, score.ctypes.data,
+                                                      L.stream_of(feats)),
+                    "sat_decoder_beam_search_batch")
+            for i in range(n):
+                alpha = alphas[i, :n_rows[i]]
+                if score[i] == float("-inf"):
+                    print("No completed sentences found")
+                    out.append(([0], torch.from_numpy(alpha.copy()), float("-inf")))
+                else:
+                    out.append((ids[i, :n_ids[i]].tolist(), alpha.tolist(), float(score[i])))
+        return out
+
     def get_init_lstm_state(self, img_features):
         """decoder.py:137-147 on HIP GEMMs (inference helper)."""
         from .ops import linear

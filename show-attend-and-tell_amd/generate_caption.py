@@ -1,7 +1,8 @@
-"""Caption one image with beam search (reference: generate_caption.py) on the MI355X path.
+"""Caption one image, or many at once, with beam search (reference: generate_caption.py) on the MI355X path.
 
     python show-attend-and-tell_amd/generate_caption.py --img-path dog.jpg --model model/model_vgg19_5.pth
     python show-attend-and-tell_amd/generate_caption.py --img-path dog.jpg --model m.pth --plot att.png
+    python show-attend-and-tell_amd/generate_caption.py --img-dir photos/ --model m.pth --plot att_dir/
 
 Same flags as the reference (generate_caption.py:153-160) plus:
   --model-config  model_config.json written by train.py (default: next to --model); the
@@ -11,6 +12,11 @@ Same flags as the reference (generate_caption.py:153-160) plus:
   --bert-vocab    a local bert-base-uncased vocab.txt (offline BertTokenizer); without it BERT
                   ids print as the [CLS]/[SEP]/[PAD]/tokN stub
   --plot          write the attention visualisation (:111-150) to this PNG (matplotlib)
+  --img-dir       caption every image file of this directory (sorted by name); --img-path may also be
+                  repeated.  Several images are encoded in batches of --batch-size (default 32) and decoded
+                  together by batched beam search (Decoder.caption_batch); one JSON line per image, with a
+                  "path" key, in input order, and --plot then names a directory that receives
+                  <stem>_att.png per image.  A single --img-path without --img-dir behaves as before
   --encoder-weights  the trunk's state_dict (weights_only); default: the encoder_weights entry
                   train.py wrote into model_config.json.  The reference relies on torchvision's
                   pretrained weights being the same everywhere; this build has none offline, so the
@@ -18,6 +24,7 @@ Same flags as the reference (generate_caption.py:153-160) plus:
 W&B restore (--wandb-run/--wandb-model) needs network access and is not supported here.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -93,6 +100,27 @@ def caption_image(img, encoder, decoder, beam_size=3):
         return decoder.caption(feats, beam_size)
 
 
+IMAGE_EXTS = (".jpg", ".jpeg", ".png", ".bmp", ".gif", ".webp", ".ppm", ".tif", ".tiff")
+
+
+def list_images(img_dir):
+    """The image files of a directory, sorted by name."""
+    return [os.path.join(img_dir, n) for n in sorted(os.listdir(img_dir))
+            if n.lower().endswith(IMAGE_EXTS) and os.path.isfile(os.path.join(img_dir, n))]
+
+
+def caption_images(paths, encoder, decoder, beam_size=3, batch_size=32):
+    """Encode ``paths`` in batches and beam-search each batch in one call; yields (path, sentence, alpha, score)."""
+    device = next(iter(decoder.parameters())).device
+    for lo in range(0, len(paths), batch_size):
+        chunk = paths[lo:lo + batch_size]
+        with torch.no_grad():
+            feats = encoder(torch.cat([load_image(p) for p in chunk], 0).to(device))
+            results = decoder.caption_batch(feats, beam_size, max_images=batch_size)
+        for path, (sentence, alpha, score) in zip(chunk, results):
+            yield path, sentence, alpha, score
+
+
 def sentence_tokens(sentence, decoder, word_dict):
     """generate_caption.py:90-101."""
     if decoder.use_bert:
@@ -142,11 +170,14 @@ def plot_attention(img_path, tokens, alpha, network, out_png):
         plt.imshow(a, alpha=0.8, cmap="Greys_r")
         plt.axis("off")
     plt.savefig(out_png, bbox_inches="tight")
+    plt.close()
 
 
 def main(argv=None):
     p = argparse.ArgumentParser(description="Show, Attend and Tell Caption Generator (MI355X)")
-    p.add_argument("--img-path", type=str, help="path to image")
+    p.add_argument("--img-path", type=str, action="append", help="path to image (may be repeated)")
+    p.add_argument("--img-dir", type=str, default=None, help="caption every image file in this directory")
+    p.add_argument("--batch-size", type=int, default=32, help="images encoded and decoded together")
     p.add_argument("--model", type=str, help="path to model parameters")
     p.add_argument("--wandb-run", type=str, default=None)
     p.add_argument("--wandb-model", type=str, default=None)
@@ -162,11 +193,30 @@ def main(argv=None):
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     encoder, decoder, cfg, word_dict = load_model(args.model, args.model_config, dt, bert_vocab=args.bert_vocab,
                                                   encoder_weights=args.encoder_weights)
-    sentence, alpha = caption_image(load_image(args.img_path), encoder, decoder, args.beam_size)
-    tokens = sentence_tokens(sentence, decoder, word_dict)
-    print(json.dumps({"caption": " ".join(tokens), "ids": sentence, "score": decoder.last_caption_score}))
+    paths = list(args.img_path or [])
+    if args.img_dir is None and len(paths) == 1:   # the reference's single-image form
+        sentence, alpha = caption_image(load_image(paths[0]), encoder, decoder, args.beam_size)
+        tokens = sentence_tokens(sentence, decoder, word_dict)
+        print(json.dumps({"caption": " ".join(tokens), "ids": sentence, "score": decoder.last_caption_score}))
+        if args.plot:
+            plot_attention(paths[0], tokens, alpha, cfg["network"], args.plot)
+        return 0
+    if args.img_dir is not None:
+        paths += list_images(args.img_dir)
+    if not paths:
+        p.error("no image: pass --img-path and/or an --img-dir that holds image files")
+    if args.batch_size < 1:
+        p.error("--batch-size must be >= 1")
     if args.plot:
-        plot_attention(args.img_path, tokens, alpha, cfg["network"], args.plot)
+        os.makedirs(args.plot, exist_ok=True)
+    with contextlib.redirect_stdout(sys.stderr):   # load / "no completed sentence" notices: stdout carries JSON
+        results = list(caption_images(paths, encoder, decoder, args.beam_size, args.batch_size))
+    for path, sentence, alpha, score in results:
+        tokens = sentence_tokens(sentence, decoder, word_dict)
+        print(json.dumps({"path": path, "caption": " ".join(tokens), "ids": sentence, "score": score}), flush=True)
+        if args.plot:
+            stem = os.path.splitext(os.path.basename(path))[0]
+            plot_attention(path, tokens, alpha, cfg["network"], os.path.join(args.plot, f"{stem}_att.png"))
     return 0
 
 

@@ -19,6 +19,9 @@ so it cannot be disabled, as in train.py:450), plus:
                   uint8 images travel at native size and sat_images_to_input resamples them on the GPU,
                   bit-identical to PIL's bilinear resize + torchvision's ToTensor / Normalize)
   --workers       decode workers per rank (default 8)
+  --beam-eval K   also caption every validation / test batch with batched beam search of width K
+                  (Decoder.caption_batch) and log {mode}_beam_bleu1..4 for the generated sentences
+                  (default 0 = off: only the reference's teacher-forced argmax BLEU)
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -26,6 +29,7 @@ Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-
 reference's scalar names are printed / written as JSON lines instead.
 """
 import argparse
+import contextlib
 import json
 import os
 import random
@@ -149,6 +153,8 @@ def parse(argv=None):
                    help="resize + normalize on the host workers (default: workers only decode; the GPU resamples "
                         "the uint8 images bit-identically to PIL and normalizes into the encoder's input layout)")
     p.add_argument("--workers", type=int, default=8, help="DataLoader decode workers per rank")
+    p.add_argument("--beam-eval", type=int, default=0,
+                   help="beam width of an extra generated-caption BLEU in evaluation (0 = off)")
     p.add_argument("--bert-embeddings", type=str, default=None,
                    help="local bert-base-uncased word-embedding table [30522, 768] (weights_only)")
     return p.parse_args(argv)
@@ -301,12 +307,13 @@ def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, l
 
 
 def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode, log):
-    """train.py:198-347 (teacher-forced greedy hypotheses, BLEU-1..4)."""
+    """train.py:198-347 (teacher-forced greedy hypotheses, BLEU-1..4); with --beam-eval K also the BLEU of the
+    sentences batched beam search generates from the same features."""
     encoder.eval()
     decoder.eval()
     pad, skip = sat_amd.special_ids(args.bert)
     losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
-    refs, hyps = [], []
+    refs, hyps, beam_hyps = [], [], []
     tok = decoder.tokenizer if args.bert else None
     inv = {i: w for w, i in word_dict.items()} if word_dict else None
     with torch.no_grad():
@@ -314,7 +321,8 @@ def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode,
             if args.max_steps and batch_idx >= args.max_steps:
                 break
             imgs, captions = imgs.to(device), captions.to(device)   # Tensor or PackedImages
-            preds, alphas = decoder(encoder(imgs, dtype=dt), captions)
+            feats = encoder(imgs, dtype=dt)
+            preds, alphas = decoder(feats, captions)
             loss, metrics = sat_amd.caption_loss(preds, alphas, captions, args.alpha_c, pad, skip)
             m = sat_amd.StepMetrics(loss, metrics).values()
             n = m["caption_length"]
@@ -328,20 +336,28 @@ def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode,
                 dec = lambda c: [str(t) for t in c if t not in (0, 3)][:c.index(1) if 1 in c else None]  # noqa: E731
             refs += [[dec(c) for c in cs] for cs in all_caps.tolist()]
             hyps += [dec(c) for c in ids]
+            if args.beam_eval > 0:
+                with contextlib.redirect_stdout(sys.stderr):   # the "no completed sentence" notices: not JSON
+                    beam_hyps += [dec(s) for s, _, _ in decoder.caption_batch(feats, args.beam_eval)]
     sums = [losses.sum, top1.sum, top5.sum, losses.count]
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         # every rank evaluated a disjoint shard (ShardSampler): gather hypotheses, references and the
         # meters' sums so the logged BLEU-1..4 and averages cover the whole split
         parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, (refs, hyps, sums))
+        dist.all_gather_object(parts, (refs, hyps, sums, beam_hyps))
         refs = [r for p in parts for r in p[0]]
         hyps = [h for p in parts for h in p[1]]
         sums = [sum(p[2][i] for p in parts) for i in range(4)]
+        beam_hyps = [h for p in parts for h in p[3]]
     n = sums[3]
     avg = [v / n if n else 0.0 for v in sums[:3]]
     b1, b2, b3, b4 = bleu_mod.bleu_1_to_4(refs, hyps)
-    log({"epoch": epoch, f"{mode}_loss": avg[0], f"{mode}_top1_acc": avg[1], f"{mode}_top5_acc": avg[2],
-         f"{mode}_bleu1": b1, f"{mode}_bleu2": b2, f"{mode}_bleu3": b3, f"{mode}_bleu4": b4})
+    rec = {"epoch": epoch, f"{mode}_loss": avg[0], f"{mode}_top1_acc": avg[1], f"{mode}_top5_acc": avg[2],
+           f"{mode}_bleu1": b1, f"{mode}_bleu2": b2, f"{mode}_bleu3": b3, f"{mode}_bleu4": b4}
+    if args.beam_eval > 0:
+        for i, b in enumerate(bleu_mod.bleu_1_to_4(refs, beam_hyps), 1):
+            rec[f"{mode}_beam_bleu{i}"] = float(b)
+    log(rec)
     return b4
 
 
