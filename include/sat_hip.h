@@ -210,6 +210,20 @@ int sat_conv1x1_frag_supported(int H, int W, int Cin, int Cout, int dtype);
  * sat_conv2d_nhwc. */
 int sat_conv1x1_frag(int N, int H, int W, int Cin, int Cout, int dtype, const void* x, const void* wf,
                      const float* b, void* y, const SatPolicy* policy, void* stream);
+/* A bottleneck's c3 and the next bottleneck's c1 in ONE launch (encoder.py:13-17, 33-36 through torchvision; the
+ * ResNet152 layer1 / layer2 blocks): y [M,N] = relu(x [M,K] . w [N,K]^T + bias + residual [M,N]) and
+ * x1 [M,N2] = relu(y . w1 [N2,N]^T + b1), M = the NHWC pixels of a 1x1 / stride-1 conv.  The c1 is computed from
+ * y's finished tile while it is still on chip (csrc/convstream.hip), so y is not read back.  Both outputs are
+ * bit-identical to the two sat_conv2d_nhwc launches.
+ * _supported: 1 if the chained kernel takes the shape -- bf16, (K, N, N2) one of (64, 256, 64), (64, 256, 128),
+ * (128, 512, 128), M * N < 2^31 -- under the policy's conv_stream: 0 auto (HBM-bound problems: at least two 32 / 64-row
+ * items per CU), 1 never, 2 every such shape.
+ * sat_conv1x1_chain runs the chained kernel when _supported, residual is non-null and every pointer is 16-byte
+ * aligned; otherwise it issues the two launches itself (so it succeeds wherever they would). */
+int sat_conv1x1_chain_supported(int64_t M, int K, int N, int N2, int dtype, const SatPolicy* policy);
+int sat_conv1x1_chain(int64_t M, int K, int N, int N2, int dtype, const void* x, const void* w, const float* bias,
+                      const void* residual, void* y, const void* w1, const float* b1, void* x1,
+                      const SatPolicy* policy, void* stream);
 /* MaxPool2d (floor mode, -inf padding) on NHWC. */
 int sat_maxpool2d_nhwc(int N, int H, int W, int C, int k, int stride, int pad, int dtype,
                        const void* x, void* y, int OH, int OW, void* stream);

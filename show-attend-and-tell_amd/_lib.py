@@ -96,6 +96,9 @@ _SIGNATURES = [
     ("sat_conv1x1_frag_supported", c_int, [c_int, c_int, c_int, c_int, c_int]),
     ("sat_conv1x1_frag", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  ctypes.POINTER(SatPolicy), c_void_p]),
+    ("sat_conv1x1_chain_supported", c_int, [c_int64, c_int, c_int, c_int, c_int, ctypes.POINTER(SatPolicy)]),
+    ("sat_conv1x1_chain", c_int, [c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, ctypes.POINTER(SatPolicy), c_void_p]),
     ("sat_maxpool2d_nhwc", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_int, c_int, c_void_p]),
     ("sat_attention_forward", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

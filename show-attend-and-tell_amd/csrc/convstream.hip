@@ -29,6 +29,10 @@
 //   * LDS image lane-linear (DMA), swizzle on the source: 16-B chunk c of row r at slot
 //     c ^ (r & 15) (rows >= 256 B) or c ^ ((r >> 1) & 7) (128-B rows) -> conflict-free
 //     ds_read_b128 fragment reads (verified for every lane group).
+//   * chained form (conv1x1_chain_kernel, sat_conv1x1_chain): one slice of whole rows; after the epilogue barrier
+//     the finished output tile is the A operand of the NEXT bottleneck's c1 (weights register-stationary like B),
+//     computed beside the whole-row stores, so the c3's output is not read back for it: (K, N -> N2) = (64, 256 -> 64),
+//     (64, 256 -> 128), (128, 512 -> 128), both outputs bit-identical to the two launches.
 #include "sat_common.h"
 
 #ifndef SAT_STREAM_WT_BYTES
@@ -40,6 +44,7 @@
 namespace {
 
 typedef __attribute__((address_space(3))) void s_lds_void;
+typedef __attribute__((address_space(3))) char s_lds_char;
 
 constexpr int S_NW = 8, S_BN = 16 * S_NW;    // 8 waves x 16 columns
 constexpr unsigned S_OOB = 0x80000000u;
@@ -54,6 +59,10 @@ struct SArgs {
   int xcd_group;                     // 1: slice = (b / 8) % slices (one M-tile sequence per XCD)
   int wt;                            // write-through output stores (sat_common.h), else write-back
   unsigned a_bytes;
+  // chained form: the next bottleneck's c1, C2[M, N2] = relu(C . B2[N2, N]^T + bias2), computed from the finished
+  // output tile while it is still in LDS (N2 is a template parameter)
+  const bf16* B2; const float* bias2; bf16* C2;
+  int wt2;                           // write-through stores of C2
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
 
@@ -75,8 +84,9 @@ __device__ __forceinline__ void s_wait_barrier(int n) {
 }
 
 // KT = K / 32 k-steps, MB = 16-row m-blocks per item (MT = 16 * MB rows), NB = 16-column n-blocks
-// per wave (the workgroup's slice is 128 * NB columns)
-template <int KT, int MB, int NB, bool RES, int ACT, bool STRIDED>
+// per wave (the workgroup's slice is 128 * NB columns), N2B = 16-column n-blocks of the chained c1's output
+// (0: no chain; 4 or 8: the slice is the whole row, N = 128 * NB, and is the chained product's K)
+template <int KT, int MB, int NB, bool RES, int ACT, bool STRIDED, int N2B = 0>
 __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
   constexpr int K = KT * 32, MT = MB * 16, ROWB = K * 2;
   constexpr int SN = S_BN * NB, RROWB = SN * 2;            // slice columns, residual row bytes
@@ -91,6 +101,13 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
   constexpr int ST = RTILE / (S_NW * 64 * 16);              // 16-B row-segment stores per lane per item
   constexpr int DMA_N = DMA_A + (RES ? DMA_R : 0);
   constexpr int CPR = RROWB / 16;                           // 16-B chunks per output row
+  // chained c1: wave w computes n-block w of all MB m-blocks (N2 = 128) or n-block w % 4 of m-half w / 4 (N2 = 64);
+  // the output tile leaves as whole rows through LDS where it fits, else m-blocks in pairs as 16-B stores
+  constexpr int N2 = 16 * N2B, KT2 = SN / 32, MB2 = N2B == 4 ? MB / 2 : MB;
+  constexpr bool X1_LDS = N2B && MT * N2 * 2 <= TILE;       // the chained output tile is staged in the A tile's LDS
+  constexpr int ST2 = N2B ? (X1_LDS ? 1 : MB2 / 2) : 0;     // 16-B chained-output stores per lane per item
+  static_assert(N2B == 0 || ((N2B == 4 || N2B == 8) && MB2 % 2 == 0), "chained c1: 64 or 128 columns, m-block pairs");
+  static_assert(DMA_N + 2 * (ST + ST2) <= 24, "s_wait_barrier's counted cases");
   __shared__ __attribute__((aligned(16))) char smem[NSTG * STG];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -122,12 +139,38 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
   for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
     for (int j = 0; j < 4; ++j) bias4[nb][j] = a.bias ? a.bias[ns + wc + nb * 16 + 4 * fh + j] : 0.f;
+  // chained c1: this wave's 16 rows of B2 for all of its K (= N), registers for the whole kernel like bq
+  const int nb2 = N2B == 4 ? (w & 3) : w, mb2 = N2B == 4 ? (w >> 2) * MB2 : 0;
+  bf16x8 wq[KT2 > 0 && N2B ? KT2 : 1];
+  float bias2[4];
+  if constexpr (N2B > 0) {
+    const bf16* wp = a.B2 + (long)(nb2 * 16 + fr) * SN + 8 * fh;
+#pragma unroll
+    for (int ks = 0; ks < KT2; ++ks) wq[ks] = *(const bf16x8*)(wp + 32 * ks);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bias2[j] = a.bias2 ? a.bias2[nb2 * 16 + 4 * fh + j] : 0.f;
+    // consume every register-stationary operand here: otherwise the compiler's vmcnt tracking still sees the
+    // loads pending inside the item loop and inserts waits that also drain the next items' DMAs and the stores
+#pragma unroll
+    for (int ks = 0; ks < KT2; ++ks) asm volatile("" ::"v"(wq[ks]));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bias2[j]));
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+      for (int ks = 0; ks < KT; ++ks) asm volatile("" ::"v"(bq[ks][nb]));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bias4[nb][j]));
+    }
+  }
 
   const unsigned c_bytes = (unsigned)((long)a.M * a.N * 2);
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, (short)0, (int)a.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)a.C, (short)0, (int)c_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rR =
       __builtin_amdgcn_make_buffer_rsrc((void*)(RES ? a.res : a.C), (short)0, (int)c_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rC2 = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(N2B ? a.C2 : a.C), (short)0, (int)(N2B ? (unsigned)((long)a.M * N2 * 2) : c_bytes), 0x00020000);
 
   // Every global read of the loop is an LDS-DMA (A tile and residual tile of the next item), so the
   // only vmcnt waits are the counted ones below; rows >= M read zeros through out-of-range buffer
@@ -190,7 +233,7 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
     // wait for this wave's DMAs of item `it`; younger: the next item's DMAs (if any) and the
     // stores of the previous one or two items -- they stay in flight across the barrier.  After it
     // every wave's DMAs of `it` have landed and every wave finished reading stage (k+2) % 3.
-    const int younger = (it + step < a.items ? DMA_N : 0) + (k >= 1 ? ST : 0) + (k >= 2 ? ST : 0);
+    const int younger = (it + step < a.items ? DMA_N : 0) + (k >= 1 ? ST + ST2 : 0) + (k >= 2 ? ST + ST2 : 0);
     s_wait_barrier(younger);
     if (nxt2 < a.items) stage(nxt2, buf == 0 ? 2 : buf - 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -245,16 +288,98 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: DMAs and stores stay in flight
+    // the row reads are asm statements with their own lgkmcnt wait: ahead of an LDS read it can see, the compiler
+    // waits for the LDS-DMAs in flight with a vmcnt(0) of its own, which drained the next items' DMAs and the last
+    // items' stores in every iteration (the barrier above already orders these reads after the epilogue's writes)
+    typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
+    u32x4 rows[ST];
 #pragma unroll
     for (int p = 0; p < ST; ++p) {
       const int t = p * S_NW * 64 + tid, r = t / CPR, lc = t % CPR;
       const int pc = (lc & ~15) | ((lc & 15) ^ (r & 15));
-      const uint4 u = *(const uint4*)(ro + r * RROWB + 16 * pc);
+      asm volatile("ds_read_b128 %0, %1" : "=v"(rows[p]) : "v"((unsigned)(uintptr_t)(s_lds_char*)(ro + r * RROWB + 16 * pc)) : "memory");
+    }
+    static_assert(ST == 1 || ST == 2 || ST == 4, "the wait below names every row register");
+    if constexpr (ST == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rows[0]), "+v"(rows[1]), "+v"(rows[2]), "+v"(rows[3]) :: "memory");
+    else if constexpr (ST == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rows[0]), "+v"(rows[1]) :: "memory");
+    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rows[0]) :: "memory");
+#pragma unroll
+    for (int p = 0; p < ST; ++p) {
+      const int t = p * S_NW * 64 + tid, r = t / CPR, lc = t % CPR;
+      const u32x4 u = rows[p];
       const int m = it * MT + r;
       const unsigned off = m < a.M ? (unsigned)(((long)m * a.N + ns + 8 * lc) * 2) : S_OOB;
-      typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-      if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(u32x4{u.x, u.y, u.z, u.w}, rC, (int)off, 0, SAT_OUT_CPOL);
-      else __builtin_amdgcn_raw_buffer_store_b128(u32x4{u.x, u.y, u.z, u.w}, rC, (int)off, 0, 0);
+      if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(u, rC, (int)off, 0, SAT_OUT_CPOL);
+      else __builtin_amdgcn_raw_buffer_store_b128(u, rC, (int)off, 0, 0);
+    }
+    if constexpr (N2B > 0) {
+      // chained c1 on the finished tile (bias, residual, activation applied, rounded once to bf16): A fragments are
+      // row mb*16 + fr, logical chunk 4 ks + fh of the R/O tile -- the A tile's read pattern and swizzle; the stage is
+      // refilled only after the next iteration's barrier.  k-steps ascending, one accumulator per output: the
+      // arithmetic of the standalone c1 launch.
+      f32x4 acc2[MB2];
+#pragma unroll
+      for (int i = 0; i < MB2; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KT2; ++ks) {
+#pragma unroll
+        for (int i = 0; i < MB2; ++i) {
+          const int r = (mb2 + i) * 16 + fr, c = ks * 4 + fh;
+          const int pc = (c & ~15) | ((c & 15) ^ (r & 15));
+          const bf16x8 xf = *(const bf16x8*)(ro + r * RROWB + 16 * pc);
+          acc2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[ks], xf, acc2[i], 0, 0, 0);
+        }
+      }
+      // lane holds C2[m0 + (mb2 + i)*16 + fr][nb2*16 + 4 fh + j], j = 0..3: bias, ReLU, one bf16 rounding
+      u32x2 o[MB2];
+#pragma unroll
+      for (int i = 0; i < MB2; ++i) {
+        u32x2 t;
+        bf16* ob = (bf16*)&t;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ob[j] = (bf16)apply_act(acc2[i][j] + bias2[j], SAT_ACT_RELU);
+        o[i] = t;
+      }
+      if constexpr (X1_LDS) {
+        // the C2 tile fits the stage's A tile (every wave read its A fragments before the barrier above, and the
+        // stage is refilled after the next one): the 8-B pieces go there, 16-B chunk c of row r at slot
+        // c ^ (r % chunks per row), and after a barrier the tile leaves as whole rows, 16 B per lane -- a
+        // write-through store of part of a row is a fabric write of its own
+        constexpr int CPR2 = N2 * 2 / 16;
+        static_assert(MT * N2 * 2 == S_NW * 64 * 16, "one 16-B row segment per lane");
+        char* xt = (char*)base;
+#pragma unroll
+        for (int i = 0; i < MB2; ++i) {
+          const int r = (mb2 + i) * 16 + fr, lc = (nb2 * 16 + 4 * fh) / 8;
+          *(u32x2*)(xt + r * (N2 * 2) + 16 * (lc ^ (r & (CPR2 - 1))) + 8 * (fh & 1)) = o[i];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const int r = tid / CPR2, lc = tid % CPR2;
+        u32x4 u;   // asm, as the row reads above
+        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(u) : "v"((unsigned)(uintptr_t)(s_lds_char*)(xt + r * (N2 * 2) + 16 * (lc ^ (r & (CPR2 - 1))))) : "memory");
+        const int m = it * MT + r;
+        const unsigned off = m < a.M ? (unsigned)(((long)m * N2 + 8 * lc) * 2) : S_OOB;
+        if (a.wt2) __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, SAT_OUT_CPOL);
+        else __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, 0);
+      } else {
+        // a larger C2 tile leaves from the registers.  Lanes fh and fh ^ 1 swap halves of an m-block pair: the even
+        // lane stores columns 4 fh .. 4 fh + 7 of m-block i, the odd one 4 (fh - 1) .. 4 fh + 3 of m-block i + 1 --
+        // whole 16-B stores; rows >= M are dropped through the out-of-range offset, so every lane issues every
+        // store (the counted vmcnt)
+        const bool odd = fh & 1;
+#pragma unroll
+        for (int i = 0; i < MB2; i += 2) {
+          const u32x2 send = odd ? o[i] : o[i + 1];
+          const unsigned gx = (unsigned)__shfl_xor((int)send.x, 16, 64), gy = (unsigned)__shfl_xor((int)send.y, 16, 64);
+          const u32x4 u = odd ? u32x4{gx, gy, o[i + 1].x, o[i + 1].y} : u32x4{o[i].x, o[i].y, gx, gy};
+          const int m = it * MT + (mb2 + i + (odd ? 1 : 0)) * 16 + fr;
+          const int col = nb2 * 16 + 4 * fh - (odd ? 4 : 0);
+          const unsigned off = m < a.M ? (unsigned)(((long)m * N2 + col) * 2) : S_OOB;
+          if (a.wt2) __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, SAT_OUT_CPOL);
+          else __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, 0);
+        }
+      }
     }
     it += step;
     if (it >= a.items) break;
@@ -269,7 +394,29 @@ __global__ __launch_bounds__(S_NW * 64) void conv1x1_stream_kernel(SArgs a) {
   sat_stamp_end(a.st, t0);
 }
 
+// the chained form (bottleneck c3 + residual + ReLU, then the next bottleneck's c1 + ReLU): one 128 * NB column
+// slice = whole output rows
+template <int KT, int MB, int NB, int N2B>
+__global__ __launch_bounds__(S_NW * 64) void conv1x1_chain_kernel(SArgs a) {
+  const SatStampT0 t0 = sat_stamp_begin(a.st);
+  conv1x1_stream_kernel_body<KT, MB, NB, true, SAT_ACT_RELU, false, N2B>(a);
+  sat_stamp_end(a.st, t0);
+}
+
 int g_stream_cus = 0;    // CU count (queried once)
+
+int stream_cus() {
+  if (g_stream_cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      return 0;
+#ifdef SAT_STREAM_CUS   // diagnostics builds: size the persistent grids for this many CUs (the rest left to a
+    n = SAT_STREAM_CUS;    // concurrent decoder)
+#endif
+    g_stream_cus = n;
+  }
+  return g_stream_cus;
+}
 
 template <int KT, int MB, int NB, bool RES, bool STRIDED>
 void launch_s(int act, dim3 grid, hipStream_t s, const SArgs& a) {
@@ -311,15 +458,7 @@ int sat_conv_stream_try(const SatGemm& g, hipStream_t s, int* err) {
   const long a_bytes = 2L * cv.N * cv.H * cv.W * cv.C;
   if (a_bytes >= (1L << 31) || (long)g.M * g.N >= (1L << 31)) return 0;
   const bool strided = cv.stride != 1 || cv.OH != cv.H || cv.OW != cv.W;
-  if (g_stream_cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      return 0;
-#ifdef SAT_STREAM_CUS   // diagnostics builds: size the persistent grids for this many CUs (the rest left to a
-    n = SAT_STREAM_CUS;    // concurrent decoder)
-#endif
-    g_stream_cus = n;
-  }
+  if (stream_cus() == 0) return 0;
   // NB = 2 (256-column slices; each A fragment read feeds two MFMAs) when N allows it, 32-row items;
   // NB = 1 (128-column slices) otherwise, 64-row items (32 at K = 512)
   const int NB = g.N % (2 * S_BN) == 0 ? 2 : 1;
@@ -371,4 +510,76 @@ int sat_conv_stream_try(const SatGemm& g, hipStream_t s, int* err) {
   }
   *err = (int)hipGetLastError();
   return 1;
+}
+
+// ---- chained form: a bottleneck's c3 + residual + ReLU and the next bottleneck's c1 + ReLU in one launch ----
+namespace {
+
+// the instantiations: (K, N -> N2) = (64, 256 -> 64), (64, 256 -> 128) [ResNet152 layer1, and into layer2],
+// (128, 512 -> 128) [layer2]; 0 = none.  Auto mode takes HBM-bound problems only (sat_conv_stream_try's rule)
+int chain_items(long M, int K, int N, int N2, int dtype) {
+  if (dtype != SAT_BF16 || M <= 0) return 0;
+  const bool l1 = K == 64 && N == 256 && (N2 == 64 || N2 == 128), l2 = K == 128 && N == 512 && N2 == 128;
+  if (!l1 && !l2) return 0;
+  if (M * N >= (1L << 31)) return 0;   // 32-bit element / buffer offsets
+  const int mode = sat_policy().conv_stream;
+  if (mode == 1) return 0;
+  const int cus = stream_cus();
+  if (cus == 0) return 0;
+  const int items = sat_cdiv(M, l1 ? 64 : 32);
+  if (mode == 0 && items < 2L * cus) return 0;
+  return items;
+}
+
+}  // namespace
+
+extern "C" int sat_conv1x1_chain_supported(int64_t M, int K, int N, int N2, int dtype, const SatPolicy* policy) {
+  SatPolicyScope scope(policy);
+  return chain_items(M, K, N, N2, dtype) > 0;
+}
+
+extern "C" int sat_conv1x1_chain(int64_t M, int K, int N, int N2, int dtype, const void* x, const void* w,
+                                 const float* bias, const void* residual, void* y, const void* w1, const float* b1,
+                                 void* x1, const SatPolicy* policy, void* stream) {
+  SAT_REQUIRE(M > 0 && M < (1L << 31) && K > 0 && N > 0 && N2 > 0 && x && w && y && w1 && x1);
+  SatPolicyScope scope(policy);
+  hipStream_t s = (hipStream_t)stream;
+  const int items = chain_items(M, K, N, N2, dtype);
+  const bool ok = items > 0 && residual && sal16(x) && sal16(w) && sal16(y) && sal16(residual) && sal16(w1) && sal16(x1) &&
+                  !(bias && ((uintptr_t)bias & 15)) && !(b1 && ((uintptr_t)b1 & 15));
+  if (!ok) {   // the two launches the chained kernel stands for, through the library's own dispatch
+    SatGemm g;
+    g.conv = SatConvGeom{1, 1, (int)M, K, 1, 1, 1, 0, 1, (int)M};
+    g.M = (int)M; g.N = N; g.K = K; g.dtype = dtype;
+    g.A = x; g.B = w; g.ldb = K; g.C = y; g.ldc = N; g.c_dtype = dtype;
+    g.bias = bias; g.add1 = residual; g.ld_add1 = N; g.add1_dtype = dtype; g.act = SAT_ACT_RELU;
+    const int e = sat_gemm_launch(g, s);
+    if (e) return e;
+    SatGemm h;
+    h.conv = SatConvGeom{1, 1, (int)M, N, 1, 1, 1, 0, 1, (int)M};
+    h.M = (int)M; h.N = N2; h.K = N; h.dtype = dtype;
+    h.A = y; h.B = w1; h.ldb = N; h.C = x1; h.ldc = N2; h.c_dtype = dtype;
+    h.bias = b1; h.act = SAT_ACT_RELU;
+    return sat_gemm_launch(h, s);
+  }
+  const int cus = stream_cus();
+  SArgs a{};
+  a.M = (int)M; a.N = N; a.K = K;
+  a.A = (const bf16*)x; a.B = (const bf16*)w; a.C = (bf16*)y;
+  a.bias = bias; a.res = (const bf16*)residual;
+  a.H = 1; a.W = (int)M; a.Cin = K; a.stride = 1; a.OH = 1; a.OW = (int)M;
+  a.slices = 1; a.per_slice = cus < items ? cus : items; a.items = items;
+  a.xcd_group = 0;
+  a.a_bytes = (unsigned)(2L * M * K);
+  // each output keeps the store policy of its separate launch: y sat_conv_stream_try's rule; x1 the same rule when
+  // the stream kernel runs that c1 (N2 = 128), the tile kernel's write-through stores at N2 = 64
+  a.wt = 2L * M * N <= (long)SAT_STREAM_WT_BYTES;
+  a.B2 = (const bf16*)w1; a.bias2 = b1; a.C2 = (bf16*)x1;
+  a.wt2 = N2 < S_BN || 2L * M * N2 <= (long)SAT_STREAM_WT_BYTES;
+  a.st = sat_launch_stamps();
+  const dim3 grid(a.per_slice), block(S_NW * 64);
+  if (K == 64 && N2 == 64) hipLaunchKernelGGL((conv1x1_chain_kernel<2, 4, 2, 4>), grid, block, 0, s, a);
+  else if (K == 64) hipLaunchKernelGGL((conv1x1_chain_kernel<2, 4, 2, 8>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((conv1x1_chain_kernel<4, 2, 4, 8>), grid, block, 0, s, a);
+  return (int)hipGetLastError();
 }

@@ -11,6 +11,8 @@ activations:
   * every Conv2d (+ eval-mode BatchNorm folded into weight/bias, + ReLU, + the
     residual add of a Bottleneck) is ONE implicit-GEMM MFMA launch
     (sat_conv2d_nhwc): M = B*OH*OW, N = Cout, K = KH*KW*Cin;
+  * in ResNet152's layer1 a block's c3 launch also computes the next block's c1 from its
+    output tile while that is still on chip (ops.conv1x1_chain; ``Encoder.chain_c1``);
   * MaxPool2d is a streaming NHWC kernel;
   * the image is converted once to NHWC with channels zero-padded 3 -> 8 so the
     first conv loads 16-byte vectors (VGG19); for ResNet152 it is converted to a
@@ -168,6 +170,12 @@ class Encoder(nn.Module):
         # ... its c1 on the half-image 1x1 kernel (sat_conv1x1_frag: input slabs by LDS-DMA, weights
         # register-direct)
         self.c1_frag = True
+        # c3 input widths (64: layer1, 128: layer2) whose c3 + residual launch also computes the NEXT unfused block's
+        # c1 from its output tile while that is still on chip (ops.conv1x1_chain, csrc/convstream.hip): the next
+        # block then launches no c1 and the c3's output is not read back for it.  set() = every c1 its own launch
+        # (A/B, tests).  Layer2 (128) is off: its chained kernel is faster than the two launches on its own but
+        # slows the overlapped train step (5.95 vs 5.90 ms)
+        self.chain_c1 = {64}
         # per-call kernel selection for the conv launches (sat_amd.Policy / SatPolicy; None = the library's
         # defaults): A/B measurements and tests only
         self.policy = None
@@ -321,13 +329,7 @@ class Encoder(nn.Module):
                 y = ops.images_to_input(x, L.IMG_NHWC, dtype, c_pad=IN_PAD)
             return self._run_plan(y, plan, stop)
         if start > 0:
-            y = x
-            for step in plan[start:stop]:
-                y = self._run_step(y, step)
-            if stop < len(plan):
-                return y
-            B, H, W, C = y.shape
-            return y.view(B, H * W, C)
+            return self._run_plan(x, plan, stop, start)
         H, W = x.shape[2], x.shape[3]
         if plan[0][0] == "stem_s2d" and H % 2 == 0 and W % 2 == 0:
             y = ops.nchw_to_s2d(x, dtype)
@@ -351,31 +353,74 @@ class Encoder(nn.Module):
         elig = [s for s in plan if s[0] == "block" and s[5] is not None and self._block_cin(s) != 512]
         return next(i for i, s in enumerate(elig) if s is step) % int(f) == 0
 
-    def _run_plan(self, y, plan, stop):
-        for step in plan[:stop]:
-            if step[0] == "stem_s2d":
-                continue
-            y = self._run_step(y, step)
+    def _run_plan(self, y, plan, stop, start=0):
+        """Plan steps start .. stop - 1.  A chained c3 hands the next block's c1 output (x1) to the next step of
+        this loop only: never past ``stop``, and a slice entered at ``start`` > 0 runs its own first c1."""
+        steps = [s for s in plan[start:stop] if s[0] != "stem_s2d"]
+        x1 = None
+        for i, step in enumerate(steps):
+            y, x1 = self._run_step(y, step, x1, steps[i + 1] if i + 1 < len(steps) else None)
         if stop < len(plan):
             return y
         B, H, W, C = y.shape
         return y.view(B, H * W, C)
 
-    def _run_step(self, y, step):
+    def _block_fused(self, step, shape, dtype):
+        """The block runs as ONE fused launch on an input of this NHWC shape."""
+        return (step[5] is not None and self._fuse_this(self._plan, step)
+                and ops.bottleneck_fused_supported(shape[1], shape[2], shape[3], step[1][0].shape[0], dtype))
+
+    def _block_c1_frag(self, step, shape, dtype):
+        return step[5] is not None and self.c1_frag and ops.conv1x1_frag_supported(shape[1], shape[2], shape[3],
+                                                                                step[1][0].shape[0], dtype)
+
+    def _chain_into(self, out, c3, nxt):
+        """The c1 weights of the next plan step when this block's c3 (input ``out``) is launched chained with it."""
+        if nxt is None or nxt[0] != "block" or out.shape[3] not in self.chain_c1:
+            return None
+        c1n = nxt[1]
+        yshape = (out.shape[0], out.shape[1], out.shape[2], c3[0].shape[0])
+        if c1n[2] != 1 or c1n[3] != 0 or c1n[0].shape[3] != yshape[3] or self._block_fused(nxt, yshape, out.dtype) \
+                or self._block_c1_frag(nxt, yshape, out.dtype):
+            return None
+        if not ops.conv1x1_chain_supported(out.shape[0] * out.shape[1] * out.shape[2], out.shape[3], yshape[3],
+                                           c1n[0].shape[0], out.dtype, self.policy):
+            return None
+        return c1n
+
+    def _absorbed(self, y, f):
+        """The bench hooks of a c1 launch the previous block's chained c3 already computed: its record in launch
+        order, an empty event pair and one launch-policy slot, so per-launch tables keep their length."""
+        w, b, s, p = f
+        if self.timing_args is not None:
+            self.timing_args.append((y, w, b, s, p, True, None, None))
+        if self.launch_policy is not None:
+            self.launch_policy()
+        if self.timing is not None:
+            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            st.record()
+            en.record()
+            self.timing.append((st, en))
+
+    def _run_step(self, y, step, x1=None, nxt=None):
+        """One plan step on activation y -> (its output, the next block's c1 output when this step's c3 was launched
+        chained with it (``nxt``: the next step of the same forward), else None).  ``x1``: this block's c1 output
+        handed over by the previous step."""
         if step[0] == "conv":
             f = step[3]
             if f is not None and self.c2_frag and y.shape[1] in self.c2_frag_sizes \
                     and ops.conv3x3_frag_supported(y.shape[1], y.shape[2], y.shape[3], y.dtype):
-                return self._frag_conv("c2frag", ops.conv3x3_frag, y, f)
-            return self._conv(y, step[1], step[2])
+                return self._frag_conv("c2frag", ops.conv3x3_frag, y, f), None
+            return self._conv(y, step[1], step[2]), None
         if step[0] == "pool":
-            return ops.maxpool2d_nhwc(y, step[1], step[2], step[3])
+            return ops.maxpool2d_nhwc(y, step[1], step[2], step[3]), None
         _, c1, c2, c3, ds, fused, c2f = step
-        if (fused is not None and self._fuse_this(self._plan, step)
-                and ops.bottleneck_fused_supported(y.shape[1], y.shape[2], y.shape[3], c1[0].shape[0], y.dtype)):
-            return self._launch(("fused", y, fused), ops.bottleneck_fused, y, *fused)
-        if fused is not None and self.c1_frag and ops.conv1x1_frag_supported(y.shape[1], y.shape[2], y.shape[3],
-                                                                           c1[0].shape[0], y.dtype):
+        if x1 is not None:   # computed by the previous block's chained c3 launch (_chain_into ruled the other forms out)
+            self._absorbed(y, c1)
+            out = x1
+        elif self._block_fused(step, y.shape, y.dtype):
+            return self._launch(("fused", y, fused), ops.bottleneck_fused, y, *fused), None
+        elif self._block_c1_frag(step, y.shape, y.dtype):
             out = self._frag_conv("c1frag", ops.conv1x1_frag, y, fused[0])
         else:
             out = self._conv(y, c1, True)
@@ -386,4 +431,8 @@ class Encoder(nn.Module):
         else:
             out = self._conv(out, c2, True)
         idn = self._conv(y, ds, False) if ds is not None else y
-        return self._conv(out, c3, True, residual=idn)
+        c1n = self._chain_into(out, c3, nxt)
+        if c1n is not None:
+            w, b, s, p = c3
+            return self._launch((out, w, b, s, p, True, idn, None), ops.conv1x1_chain, out, c3, idn, c1n)
+        return self._conv(out, c3, True, residual=idn), None

@@ -260,6 +260,33 @@ def conv1x1_frag(x, f, out=None, policy=None):
     return y
 
 
+def conv1x1_chain_supported(M, K, N, N2, dtype, policy=None):
+    """True when conv1x1_chain runs (M pixels, K -> N channels, then N -> N2) as ONE launch under ``policy``."""
+    return bool(L.lib().sat_conv1x1_chain_supported(M, K, N, N2, L.dtype_code(dtype), L.policy_ptr(policy)))
+
+
+def conv1x1_chain(x, c3, residual, c1_next, policy=None):
+    """A bottleneck's c3 and the next bottleneck's c1: y = relu(conv1x1(x, c3) + residual) and
+    x1_next = relu(conv1x1(y, c1_next)), with c3 / c1_next = (w [Cout,1,1,Cin], bias f32, ...) as the Encoder plan
+    folds them.  One launch when conv1x1_chain_supported (the c1 reads y's tile on chip), else the library issues
+    the two launches; either way both outputs are bit-identical to two conv2d_nhwc calls.  -> (y, x1_next)"""
+    L.require_device(x, c3[0], c1_next[0])
+    if not (x.is_contiguous() and residual.is_contiguous()):
+        raise ValueError("conv1x1_chain: x and residual must be contiguous NHWC tensors")
+    B, H, W, K = x.shape
+    w, b, w1, b1 = c3[0], c3[1], c1_next[0], c1_next[1]
+    N, N2 = w.shape[0], w1.shape[0]
+    assert tuple(w.shape[1:]) == (1, 1, K) and tuple(w1.shape[1:]) == (1, 1, N), (w.shape, w1.shape, x.shape)
+    assert w.dtype == x.dtype and w1.dtype == x.dtype
+    y = torch.empty(B, H, W, N, device=x.device, dtype=x.dtype)
+    assert residual.shape == y.shape and residual.dtype == y.dtype
+    x1 = torch.empty(B, H, W, N2, device=x.device, dtype=x.dtype)
+    L.check(L.lib().sat_conv1x1_chain(B * H * W, K, N, N2, L.dtype_code(x.dtype), L.ptr(x), L.ptr(w), L.ptr(b),
+                                      L.ptr(residual), L.ptr(y), L.ptr(w1), L.ptr(b1), L.ptr(x1),
+                                      L.policy_ptr(policy), L.stream_of(y)), "sat_conv1x1_chain")
+    return y, x1
+
+
 def maxpool2d_nhwc(x, k, stride, pad=0):
     L.require_device(x)
     N, H, W, C = x.shape
