@@ -274,6 +274,36 @@ int sat_decoder_backward(const SatDecoderDims* d, const SatDecoderLayout* lay, c
                          int phase, void* stream);   /* phase 1 | 2 | 3, + 4: d_preds already ReLU-masked (ado),
                                                      + 8: d_preds rows zero-padded to the bf16 head's
                                                      stride (sat_caption_loss_backward_ld; ado needs 4) */
+/* sat_decoder_backward that also returns dL/d(img_features) -- what loss.backward() leaves in the reference's
+ * encoder output (encoder.py:13-17 never freezes it; attention.py:14-21, decoder.py:101-105,137-147):
+ *   d_features[b,l,:] = sum_t alpha[b,t,l] dL/dcontext_t[b,:]            (the context, attention.py:19-20)
+ *                     + (dL/dWs . attention.W.weight)[b,l,:]             (the attention projection, attention.py:16)
+ *                     + (dL/d[init_h | init_c pre-activations] . [init_h.weight; init_c.weight])[b,:] / L
+ * (without attention the first two are sum_t (d gates_t . W_ih[:, E:] + d f_z,t . f_z.weight)[b,:] / L).
+ * d_features: [B,L,D] in the features' dtype, overwritten (never accumulated into) by the call's phase 2 and left
+ * untouched by a phase-1-only call; fg_workspace: sat_decoder_feature_grad_workspace_bytes(d) bytes, 16-byte
+ * aligned, used by phase 2 only (it needs no content from phase 1 or the forward).  With d_features == NULL the
+ * call is exactly sat_decoder_backward (fg_workspace is ignored).  Capturable like every other entry. */
+int sat_decoder_backward_features(const SatDecoderDims* d, const SatDecoderLayout* lay, const float* params,
+                                  const void* params_lp, const void* img_features, void* workspace,
+                                  size_t workspace_bytes, const void* preds, const float* alphas,
+                                  const void* d_preds, const float* d_alphas, float* grads, int accumulate,
+                                  int phase, void* stream, void* d_features, void* fg_workspace,
+                                  size_t fg_workspace_bytes);
+/* bytes of sat_decoder_backward_features' fg_workspace (every step's dL/dcontext [B (T-1), D] fp32, the fp32
+ * attention.W product [B L, D], the init product [B, D]); 0 for unsupported dims.  sat_decoder_workspace_bytes
+ * is unaffected. */
+size_t sat_decoder_feature_grad_workspace_bytes(const SatDecoderDims* d);
+/* The accumulation kernel of the above on its own:
+ *   out[b,l,:] = sum_{t < T1} alpha[b,t,l] dctx[b,t,:] + mean_term[b,:] / L + addend[b,l,:]
+ * summed in fp32 in step order and rounded once to dtype (SAT_F32 / SAT_BF16).  Element strides: alpha[b,t,l] at
+ * b alpha_stride_b + t alpha_stride_t + l; dctx[b,t,:] at b dctx_stride_b + t dctx_stride_t; rows b L + l of
+ * addend / out at addend_ld / out_ld; row b of mean_term at mean_ld.  addend and mean_term are nullable.
+ * D % 8 == 0, 1 <= L <= 1024, T1 >= 1, 16-byte aligned rows (fp32 strides multiples of 4, out_ld of 16 bytes). */
+int sat_feature_grad_accumulate(int B, int L, int D, int T1, int dtype, const float* alpha, int64_t alpha_stride_b,
+                                int64_t alpha_stride_t, const float* dctx, int64_t dctx_stride_b,
+                                int64_t dctx_stride_t, const float* addend, int64_t addend_ld,
+                                const float* mean_term, int64_t mean_ld, void* out, int64_t out_ld, void* stream);
 
 /* --- beam-search captioning (decoder.py:160-269, Decoder.caption; generate_caption.py:86-88) ---
  * img_features: DEVICE [beam_size, L, D] (the reference expands one image to beam rows).

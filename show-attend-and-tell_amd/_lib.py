@@ -115,6 +115,14 @@ _SIGNATURES = [
     ("sat_decoder_backward", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout), c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    ("sat_decoder_backward_features", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout),
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                              c_void_p, c_size_t]),
+    ("sat_decoder_feature_grad_workspace_bytes", c_size_t, [ctypes.POINTER(SatDecoderDims)]),
+    ("sat_feature_grad_accumulate", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                                            c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                            c_int64, c_void_p]),
     ("sat_decoder_step_bench", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout), c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p]),

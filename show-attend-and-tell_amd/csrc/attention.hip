@@ -390,6 +390,7 @@ __device__ __forceinline__ void attn_bwd1_kernel_body(AttnBwdArgs a) {
       const float dgp = dg * cx * g * (1.f - g);
       a.d_gpre[(long)b * a.d_gpre_ld + dcol] = dgp;
       if (a.d_gpre_t) ((T*)a.d_gpre_t)[(long)b * a.d_gpre_ld + dcol] = (T)dgp;
+      if (a.d_ctx_out) a.d_ctx_out[(long)b * a.d_ctx_out_ld + dcol] = dctx;
     }
     s_dctx[tid] = dctx;
   }
@@ -552,7 +553,8 @@ __global__ __launch_bounds__(BNW * 64) void attn_bwd2_kernel(AttnBwdArgs a, int 
 // left half of it idle).  The softmax backward needs sum_k alpha_k dL/dalpha_k over ALL slots; it is
 //   sum_k alpha_k (a_k . dctx + dalpha_ext_k) = ctx . dctx + sum_k alpha_k dalpha_ext_k
 // (ctx = sum_k alpha_k a_k is the saved pre-gate context), so no workgroup needs another's dL/dalpha.
-// Phases: A thread per column d: dL/dcontext (+ gate gradient, chunk 0 writes it) and ctx . dctx;
+// Phases: A thread per column d: dL/dcontext (+ gate gradient and, when asked for, dL/dcontext itself: chunk 0 writes
+// them) and ctx . dctx;
 // B wave per slot: dL/dalpha_l; C de_l = alpha_l (dL/dalpha_l - sum); D tanh backward of the chunk's
 // slots: partial dL/d(U h), dL/dv, dL/dv.bias.  With NL > 1 the partials meet in the last-arriving
 // workgroup of the row (agent-scope ticket; payload stored and loaded sc1, so no cache fence is needed:
@@ -687,6 +689,7 @@ __device__ __forceinline__ void attn_bwd_split_kernel_body(AttnBwdArgs a) {
           const float dgp = dg * cx * g * (1.f - g);
           a.d_gpre[(long)b * a.d_gpre_ld + d] = dgp;
           if (a.d_gpre_t) ((T*)a.d_gpre_t)[(long)b * a.d_gpre_ld + d] = (T)dgp;
+          if (a.d_ctx_out) a.d_ctx_out[(long)b * a.d_ctx_out_ld + d] = dctx;
         }
       }
       s_dctx[d] = dctx;
@@ -978,6 +981,104 @@ __global__ __launch_bounds__(DWS_WAVES * 64) void attn_dws_kernel(const T* Ws, c
   }
 }
 
+// After the time loop: dL/d(img_features)[b,l,:] = sum_t alpha[b,t,l] dctx[b,t,:] + mean_term[b,:] / L + addend[b,l,:]
+// (the context path of attention.py:19-20, the init_h / init_c path of decoder.py:137-147 and the finished
+// attention.W product), rounded once to T.  Workgroup (b, 32 slots, 64 x FGV columns): wave w owns FGL_LG = 8 of the
+// slots, a lane 16 bytes of output columns (FGV = 4 fp32 / 8 bf16), so the accumulators are 8 x FGV registers.  They
+// start from addend + mean_term / L (the fp32 addend is the largest stream: every row is requested up front and
+// arrives under the staging), then take alpha dctx for t = 0 .. T1-1 in fp32 (fixed order, no atomics).  Each chunk
+// of FGL_TCH steps of the tile's dctx columns and of the slots' alpha is staged in LDS once per workgroup (16-B
+// loads; stored so that a lane's 16-B LDS reads are conflict-free) and read by all four waves: any caption length,
+// and a dctx row is fetched ceil(L / 32) times.  Plain global addressing (no buffer resources: the addend alone
+// passes 2 GiB at large B L D).  Measured at B 128, bf16, back to back (L 49 D 2048 T1 26 | L 196 D 512 T1 31): 24.2 |
+// 26.2 us; not kept: a thread per 8 slots x FGV columns reading its dctx rows straight from L2 (each row fetched
+// ceil(L / 8) times) 29.9 | 31.2 us, 8 waves (64 slots) per workgroup 28.7 | 29.7 us.
+constexpr int FGL_WAVES = 4, FGL_LG = 8, FGL_TCH = 16;
+template <typename T>
+__global__ __launch_bounds__(FGL_WAVES * 64) void feature_grad_kernel(FeatureGradArgs a) {
+  constexpr int FGV = 16 / sizeof(T), H = FGV / 4;
+  constexpr int COLS = 64 * FGV, SLOTS = FGL_WAVES * FGL_LG, NT = FGL_WAVES * 64;
+  __shared__ float4 s_dc[FGL_TCH][H * 64];
+  __shared__ float s_al[FGL_TCH][SLOTS];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int L = a.L, T1 = a.T1;
+  const int l0w = blockIdx.y * SLOTS, l0 = l0w + w * FGL_LG;
+  const long d0 = (long)blockIdx.z * COLS, d = d0 + lane * FGV;
+  const bool dok = d < a.D;
+  float acc[FGL_LG][FGV];
+  {
+    float m[FGV];
+#pragma unroll
+    for (int j = 0; j < FGV; ++j) m[j] = 0.f;
+    if (a.mean_term && dok) {
+      const float inv = 1.0f / (float)L;
+#pragma unroll
+      for (int j = 0; j < FGV; j += 4) {
+        const float4 v = *(const float4*)(a.mean_term + (long)b * a.mean_ld + d + j);
+        m[j] = v.x * inv; m[j + 1] = v.y * inv; m[j + 2] = v.z * inv; m[j + 3] = v.w * inv;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < FGL_LG; ++r) {
+      const bool ok = a.addend && dok && l0 + r < L;
+#pragma unroll
+      for (int j = 0; j < FGV; j += 4) {
+        const float4 g = ok ? *(const float4*)(a.addend + ((long)b * L + l0 + r) * a.addend_ld + d + j)
+                            : make_float4(0.f, 0.f, 0.f, 0.f);
+        acc[r][j] = g.x + m[j]; acc[r][j + 1] = g.y + m[j + 1]; acc[r][j + 2] = g.z + m[j + 2];
+        acc[r][j + 3] = g.w + m[j + 3];
+      }
+    }
+  }
+  const float* al = a.alpha + (long)b * a.alpha_bs + l0w;
+  const float* dc = a.dctx + (long)b * a.dctx_bs + d0;
+  for (int c0 = 0; c0 < T1; c0 += FGL_TCH) {
+    const int tc = min(FGL_TCH, T1 - c0);
+    __syncthreads();   // the previous chunk's reads are done
+    for (int i = tid; i < tc * H * 64; i += NT) {
+      const int t = i / (H * 64), q = i % (H * 64);   // q: the row's q-th group of 4 columns -> lane q / H, half q % H
+      const float4 v = d0 + q * 4 < a.D ? *(const float4*)(dc + (long)(c0 + t) * a.dctx_ts + q * 4)
+                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+      s_dc[t][(q % H) * 64 + q / H] = v;
+    }
+    for (int i = tid; i < tc * SLOTS; i += NT) {
+      const int t = i / SLOTS, r = i % SLOTS;
+      s_al[t][r] = l0w + r < L ? al[(long)(c0 + t) * a.alpha_ts + r] : 0.f;
+    }
+    __syncthreads();
+    if (l0 >= L) continue;   // wave-uniform: a wave past the last slot only stages
+#pragma unroll 4
+    for (int t = 0; t < tc; ++t) {
+      float x[FGV];
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float4 v = s_dc[t][h * 64 + lane];
+        x[4 * h] = v.x; x[4 * h + 1] = v.y; x[4 * h + 2] = v.z; x[4 * h + 3] = v.w;
+      }
+      const float4 a0 = *(const float4*)&s_al[t][w * FGL_LG], a1 = *(const float4*)&s_al[t][w * FGL_LG + 4];
+      const float wt[FGL_LG] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+      for (int r = 0; r < FGL_LG; ++r)
+#pragma unroll
+        for (int j = 0; j < FGV; ++j) acc[r][j] = fmaf(wt[r], x[j], acc[r][j]);
+    }
+  }
+  if (!dok) return;
+#pragma unroll
+  for (int r = 0; r < FGL_LG; ++r) {
+    uint4 u;
+    if constexpr (sizeof(T) == 2) {
+      bf16* h = (bf16*)&u;
+#pragma unroll
+      for (int j = 0; j < FGV; ++j) h[j] = (bf16)acc[r][j];
+    } else {
+      u = make_uint4(__float_as_uint(acc[r][0]), __float_as_uint(acc[r][1]), __float_as_uint(acc[r][2]),
+                     __float_as_uint(acc[r][3]));
+    }
+    if (l0 + r < L) *(uint4*)((T*)a.out + ((long)b * L + l0 + r) * a.out_ld + d) = u;
+  }
+}
+
 // e-chunks per lane: 1, 2 or 4 (E <= 1024)
 inline int e_chunks(int E, int VN) {
   const int c = sat_cdiv(E, 64 * VN);
@@ -1107,6 +1208,39 @@ int sat_attention_dws_launch(const void* Ws, const float* uh_all, const float* d
     hipLaunchKernelGGL(attn_dws_kernel<float>, grid, dim3(DWS_WAVES * 64), 0, s, (const float*)Ws, uh_all, de_all, v_w, B, L, E,
                        T1, n_ech, n_lg, out_f32, (float*)out_t);
   return (int)hipGetLastError();
+}
+
+int sat_feature_grad_launch(const FeatureGradArgs& a, hipStream_t s) {
+  SAT_REQUIRE(a.B > 0 && a.L > 0 && a.L <= kMaxL && a.D > 0 && a.D % 8 == 0 && a.T1 > 0);
+  SAT_REQUIRE(a.dtype == SAT_F32 || a.dtype == SAT_BF16);
+  SAT_REQUIRE(a.alpha && a.dctx && a.out);
+  const int fgv = a.dtype == SAT_BF16 ? 8 : 4;
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  // 16-byte rows: the kernel's vector loads and stores
+  SAT_REQUIRE(al16(a.dctx) && a.dctx_bs % 4 == 0 && a.dctx_ts % 4 == 0);
+  SAT_REQUIRE(al16(a.out) && a.out_ld % fgv == 0 && a.out_ld >= a.D);
+  SAT_REQUIRE(!a.addend || (al16(a.addend) && a.addend_ld % 4 == 0 && a.addend_ld >= a.D));
+  SAT_REQUIRE(!a.mean_term || (al16(a.mean_term) && a.mean_ld % 4 == 0 && a.mean_ld >= a.D));
+  SAT_REQUIRE(sat_cdiv(a.D, 64 * fgv) <= 65535);   // grid.z; grid.y <= kMaxL / 32
+  const dim3 grid(a.B, sat_cdiv(a.L, FGL_WAVES * FGL_LG), sat_cdiv(a.D, 64 * fgv));
+  if (a.dtype == SAT_BF16) hipLaunchKernelGGL(feature_grad_kernel<bf16>, grid, dim3(FGL_WAVES * 64), 0, s, a);
+  else hipLaunchKernelGGL(feature_grad_kernel<float>, grid, dim3(FGL_WAVES * 64), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sat_feature_grad_accumulate(int B, int L, int D, int T1, int dtype, const float* alpha,
+                                           int64_t alpha_stride_b, int64_t alpha_stride_t, const float* dctx,
+                                           int64_t dctx_stride_b, int64_t dctx_stride_t, const float* addend,
+                                           int64_t addend_ld, const float* mean_term, int64_t mean_ld, void* out,
+                                           int64_t out_ld, void* stream) {
+  FeatureGradArgs a{};
+  a.B = B; a.L = L; a.D = D; a.T1 = T1; a.dtype = dtype;
+  a.alpha = alpha; a.alpha_bs = alpha_stride_b; a.alpha_ts = alpha_stride_t;
+  a.dctx = dctx; a.dctx_bs = dctx_stride_b; a.dctx_ts = dctx_stride_t;
+  a.addend = addend; a.addend_ld = addend_ld;
+  a.mean_term = mean_term; a.mean_ld = mean_ld;
+  a.out = out; a.out_ld = out_ld;
+  return sat_feature_grad_launch(a, (hipStream_t)stream);
 }
 
 int sat_attention_bwd_chunks(int B, int L, int wg_target) {

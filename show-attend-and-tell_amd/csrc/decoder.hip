@@ -243,6 +243,22 @@ size_t carve(const SatDecoderDims& d, char* base, WS* w) {
   return c.off + 256;
 }
 
+// The feature gradient's own workspace (sat_decoder_backward_features): dL/dcontext of every step [R, D] (with
+// attention: stored by the attention backward; without: the per-row products through W_ih[:, E:] and f_z), the fp32
+// attention.W product [B L, D] (attention only) and the init_h / init_c product [B, D].
+struct FGWS {
+  float *dctx, *addend, *mean_term;
+};
+size_t carve_fg(const SatDecoderDims& d, char* base, FGWS* w) {
+  const size_t B = d.B, L = d.L, D = d.D, R = B * (d.T - 1), f = 4;
+  Carver c{base};
+  c.take(w->dctx, R * D * f);
+  if (d.attention) c.take(w->addend, B * L * D * f);
+  else w->addend = nullptr;
+  c.take(w->mean_term, B * D * f);
+  return c.off + 256;
+}
+
 __global__ void start_tokens_kernel(int32_t* tok, int B, int T1, int start) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) tok[(long)b * T1] = start;
@@ -487,7 +503,9 @@ int bwd_ggemm(const Ctx& c, const WS& w, const Splits& sp, int t, hipStream_t s)
                       w.dgated, D, s, nullptr, 0, sp.g, (long)B * D);
 }
 
-int bwd_attn(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, int t, hipStream_t s) {
+// dctx_all: nullable [B, T-1, D] fp32, this step's dL/dcontext rows are stored into it (the feature gradient)
+int bwd_attn(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, int t, hipStream_t s,
+             float* dctx_all = nullptr) {
   const SatDecoderDims& d = c.d;
   const int B = d.B, L = d.L, D = d.D, E = d.E;
   const long T1 = c.T1, HG = c.HG;
@@ -502,6 +520,7 @@ int bwd_attn(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, int 
   a.gate = w.gate_all + (long)t * D; a.gate_ld = T1 * D;
   a.ctx = w.ctx_all + (long)t * D; a.ctx_ld = T1 * D;
   a.d_ctx_ext = d.ado ? w.dctx_head + (long)t * D : nullptr; a.d_ctx_ext_ld = T1 * D;
+  a.d_ctx_out = dctx_all ? dctx_all + (long)t * D : nullptr; a.d_ctx_out_ld = T1 * D;
   a.d_uh = w.dhg + (long)t * HG; a.d_uh_ld = T1 * HG; a.d_uh_t = c.at(w.dhg_t, (long)t * HG);
   a.d_gpre = w.dhg + (long)t * HG + E; a.d_gpre_ld = T1 * HG; a.d_gpre_t = c.at(w.dhg_t, (long)t * HG + E);
   a.de_out = w.de_all + (long)t * L; a.de_ld = T1 * L; a.dv_acc = w.dv_acc; a.dbv_acc = w.dbv_acc; a.part = w.part;
@@ -844,13 +863,20 @@ extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLay
   return 0;
 }
 
-extern "C" int sat_decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
-                                    const void* params_lp, const void* img_features, void* workspace,
-                                    size_t workspace_bytes, const void* preds, const float* alphas,
-                                    const void* d_preds, const float* d_alphas, float* grads, int accumulate,
-                                    int phase, void* stream) {
+namespace {
+// sat_decoder_backward, and with d_features the gradient with respect to img_features besides (written by phase 2)
+int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params, const void* params_lp,
+                     const void* img_features, void* workspace, size_t workspace_bytes, const void* preds,
+                     const float* alphas, const void* d_preds, const float* d_alphas, float* grads, int accumulate,
+                     int phase, void* stream, void* d_features, void* fg_workspace, size_t fg_workspace_bytes) {
   SAT_CHECK((hipError_t)check_dims(dp));
   SAT_REQUIRE(lay && params && img_features && workspace && preds && alphas && d_preds && d_alphas && grads);
+  FGWS fg{};
+  if (d_features && (phase & 2)) {
+    SAT_REQUIRE(fg_workspace && carve_fg(*dp, nullptr, &fg) <= fg_workspace_bytes);
+    SAT_REQUIRE(((uintptr_t)d_features & 15) == 0 && ((uintptr_t)fg_workspace & 15) == 0);
+    carve_fg(*dp, (char*)fg_workspace, &fg);
+  }
   // bit 4: d_preds already ReLU-masked (sat_caption_loss_backward_relu); bit 8: d_preds rows at the head's padded
   // stride with zero pad columns (sat_caption_loss_backward_ld), so no copy into padded rows
   SAT_REQUIRE((phase & 3) != 0 && phase >= 1 && phase <= 15);
@@ -1020,7 +1046,7 @@ extern "C" int sat_decoder_backward(const SatDecoderDims* dp, const SatDecoderLa
         SAT_CHECK((hipError_t)bwd_ggemm(c, w, sp, t, s));
       }
       StepTimer st(d, 6, t);
-      SAT_CHECK((hipError_t)bwd_attn(c, w, sp, io, t, s));
+      SAT_CHECK((hipError_t)bwd_attn(c, w, sp, io, t, s, fg.dctx));
     }
     StepTimer st(d, 7, t);
     SAT_CHECK((hipError_t)bwd_dhgemm(c, w, sp, t, s));
@@ -1063,7 +1089,56 @@ extern "C" int sat_decoder_backward(const SatDecoderDims* dp, const SatDecoderLa
     else
       SAT_CHECK((hipError_t)sat_embed_scatter_add(w.demb, w.tok, R, E, G(lay->embedding), s));
   }
-  return 0;
+  if (!fg.dctx) return 0;
+
+  // ---------------- dL/d(img_features) (attention.py:14-21, decoder.py:101-105,137-147) ----------------
+  // mean path: d[init_h | init_c pre-activations] . [init_h.weight; init_c.weight], spread over the L slots as / L
+  SAT_CHECK((hipError_t)dgrad(15, B, D, 2 * E, w.dpre0_t, 2 * E, c.W(lay->init_w), D, fg.mean_term, D));
+  if (att) {
+    // attention projection: dWs . attention.W.weight; the context path's dL/dcontext rows were stored by the loop
+    SAT_CHECK((hipError_t)dgrad(14, B * L, D, E, w.dWs_t, E, c.W(lay->attW_w), D, fg.addend, D));
+  } else {
+    // uniform attention: every step's context is the mean, so its dL/dcontext rows (d gates . W_ih[:, E:], with the
+    // ado head d f_z . f_z.weight besides) all land on the mean: per-row products, summed over t in fp32 by the
+    // accumulation below with the forward's constant alpha = 1 / L
+    if (d.ado) SAT_CHECK((hipError_t)dgrad(8, R, D, E, w.dfz_t, E, c.W(lay->fz_w), D, w.dctx_head, D));
+    SAT_CHECK((hipError_t)dgrad(14, R, D, 4 * E, dg_t, HG, c.W(lay->wih + E), E + D, fg.dctx, D,
+                                d.ado ? w.dctx_head : nullptr, D));
+  }
+  FeatureGradArgs fa{};
+  fa.B = B; fa.L = L; fa.D = D; fa.T1 = T1; fa.dtype = d.dtype;
+  fa.alpha = alphas; fa.alpha_bs = (long)T1 * L; fa.alpha_ts = L;
+  fa.dctx = fg.dctx; fa.dctx_bs = (long)T1 * D; fa.dctx_ts = D;
+  fa.addend = fg.addend; fa.addend_ld = D;
+  fa.mean_term = fg.mean_term; fa.mean_ld = D;
+  fa.out = d_features; fa.out_ld = D;
+  return sat_feature_grad_launch(fa, s);
+}
+}  // namespace
+
+extern "C" int sat_decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
+                                    const void* params_lp, const void* img_features, void* workspace,
+                                    size_t workspace_bytes, const void* preds, const float* alphas,
+                                    const void* d_preds, const float* d_alphas, float* grads, int accumulate,
+                                    int phase, void* stream) {
+  return decoder_backward(dp, lay, params, params_lp, img_features, workspace, workspace_bytes, preds, alphas, d_preds,
+                          d_alphas, grads, accumulate, phase, stream, nullptr, nullptr, 0);
+}
+
+extern "C" int sat_decoder_backward_features(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
+                                             const void* params_lp, const void* img_features, void* workspace,
+                                             size_t workspace_bytes, const void* preds, const float* alphas,
+                                             const void* d_preds, const float* d_alphas, float* grads, int accumulate,
+                                             int phase, void* stream, void* d_features, void* fg_workspace,
+                                             size_t fg_workspace_bytes) {
+  return decoder_backward(dp, lay, params, params_lp, img_features, workspace, workspace_bytes, preds, alphas, d_preds,
+                          d_alphas, grads, accumulate, phase, stream, d_features, fg_workspace, fg_workspace_bytes);
+}
+
+extern "C" size_t sat_decoder_feature_grad_workspace_bytes(const SatDecoderDims* d) {
+  if (check_dims(d)) return 0;
+  FGWS w;
+  return carve_fg(*d, nullptr, &w);
 }
 
 // Diagnostics (bench.py roofline of the per-step decoder kernels): after a forward + backward on the

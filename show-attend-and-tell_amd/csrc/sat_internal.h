@@ -113,6 +113,8 @@ struct AttnBwdArgs {
   const float* gate; long gate_ld;
   const float* ctx; long ctx_ld;
   const float* d_ctx_ext; long d_ctx_ext_ld;      // extra dL/dcontext (ado head), nullable
+  float* d_ctx_out; long d_ctx_out_ld;            // out fp32 dL/dcontext of this step [B,D] (the feature gradient's
+                                                  // operand, sat_feature_grad_launch), nullable = not stored
   float* d_uh; long d_uh_ld;            // out fp32 dL/d(U h)  (== dL/dU_b rows)
   void* d_uh_t;                         // out dtype copy (same ld), nullable
   float* d_gpre; long d_gpre_ld;        // out fp32 dL/d(f_beta h + b)
@@ -131,6 +133,21 @@ int sat_attention_bwd_launch(const AttnBwdArgs& a, hipStream_t s);
 // BPTT order), after the time loop: fp32 rows (out_f32) and a dtype copy (out_t).
 int sat_attention_dws_launch(const void* Ws, const float* uh_all, const float* de_all, const float* v_w, int B,
                              int L, int E, int T1, int dtype, float* out_f32, void* out_t, hipStream_t s);
+
+// dL/d(img_features) after the time loop (attention.py:14-21, decoder.py:137-147 backward):
+//   out[b,l,:] = sum_{t = 0 .. T1-1} alpha[b,t,l] dctx[b,t,:] + mean_term[b,:] / L + addend[b,l,:]
+// rounded once to `dtype`.  Element strides: alpha[b,t,l] at b * alpha_bs + t * alpha_ts + l, dctx[b,t,:] at
+// b * dctx_bs + t * dctx_ts, addend / out row b * L + l at stride addend_ld / out_ld, mean_term row b at mean_ld.
+// addend and mean_term are nullable.  D % 8 == 0, L <= 1024, 16-byte aligned rows; plain global addressing (any size).
+struct FeatureGradArgs {
+  int B, L, D, T1, dtype;
+  const float* alpha; long alpha_bs, alpha_ts;
+  const float* dctx; long dctx_bs, dctx_ts;
+  const float* addend; long addend_ld;
+  const float* mean_term; long mean_ld;
+  void* out; long out_ld;
+};
+int sat_feature_grad_launch(const FeatureGradArgs& a, hipStream_t s);
 
 // ---- LSTMCell pointwise (decoder.py:115, nn.LSTMCell gate order i,f,g,o) ----
 struct LstmFwdArgs {

@@ -17,7 +17,9 @@ MI355X-specific internals:
     that run the whole T-1 step loop on the GPU stream.
 The dtype of ``img_features`` selects the mode: float32 = exact parity path
 (fp32 MFMA), bfloat16 = performance path (bf16 operands, fp32 accumulation,
-bf16 ``preds``).
+bf16 ``preds``).  ``img_features`` that require grad receive their gradient (in
+their own dtype) from the backward, as the reference's encoder output does;
+features that do not cost nothing extra.
 """
 import ctypes
 import weakref
@@ -322,6 +324,10 @@ class Decoder(nn.Module):
         self._ensure_flat(img_features.device)
         if img_features.dtype == torch.bfloat16:
             self._ensure_lp()
+        if self._defer_phase2 and img_features.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("sat_amd.Decoder: img_features require grad while defer_recurrent_backward(True) is "
+                               "set: autograd's backward then ends before phase 2, which computes the feature "
+                               "gradient; detach the features or turn the deferral off")
         params = [p for n, p in self.named_parameters()]
         preds, alphas = _DecoderFn.apply(img_features.contiguous(), captions.contiguous().long(), self, *params)
         if self.use_advanced_deep_output:
@@ -524,13 +530,32 @@ class _DecoderFn(torch.autograd.Function):
             phases = (1, 2)
         else:
             phases = (3,)
+        # dL/d(img_features) (what the reference's loss.backward() leaves in the encoder output): phase 2 writes it
+        d_feats = fg_ws = None
+        fg_bytes = 0
+        if ctx.needs_input_grad[0]:
+            if dec._defer_phase2:
+                raise RuntimeError("sat_amd.Decoder.backward: img_features require grad but the recurrent backward "
+                                   "is deferred (defer_recurrent_backward)")
+            fg_bytes = lib.sat_decoder_feature_grad_workspace_bytes(ctypes.byref(ctx.dims))
+            if fg_bytes == 0:
+                raise RuntimeError("sat_amd.Decoder.backward: unsupported shape for the feature gradient")
+            fg_ws = torch.empty(fg_bytes, device=feats.device, dtype=torch.uint8)
+            d_feats = torch.empty_like(feats)
         for phase in phases:
-            L.check(lib.sat_decoder_backward(ctypes.byref(ctx.dims), ctypes.byref(ctx.lay), L.ptr(dec._flat),
-                                             L.ptr(ctx.lp), L.ptr(feats), L.ptr(ctx.ws), ctx.ws_bytes, L.ptr(preds),
-                                             L.ptr(alphas), L.ptr(d_preds), L.ptr(d_alphas),
-                                             L.ptr(dec._grad_flat), int(accumulate), phase | masked,
-                                             L.stream_of(preds)),
-                    "sat_decoder_backward")
+            if d_feats is not None and phase & 2:
+                L.check(lib.sat_decoder_backward_features(
+                    ctypes.byref(ctx.dims), ctypes.byref(ctx.lay), L.ptr(dec._flat), L.ptr(ctx.lp), L.ptr(feats),
+                    L.ptr(ctx.ws), ctx.ws_bytes, L.ptr(preds), L.ptr(alphas), L.ptr(d_preds), L.ptr(d_alphas),
+                    L.ptr(dec._grad_flat), int(accumulate), phase | masked, L.stream_of(preds), L.ptr(d_feats),
+                    L.ptr(fg_ws), fg_bytes), "sat_decoder_backward_features")
+            else:
+                L.check(lib.sat_decoder_backward(ctypes.byref(ctx.dims), ctypes.byref(ctx.lay), L.ptr(dec._flat),
+                                                 L.ptr(ctx.lp), L.ptr(feats), L.ptr(ctx.ws), ctx.ws_bytes,
+                                                 L.ptr(preds), L.ptr(alphas), L.ptr(d_preds), L.ptr(d_alphas),
+                                                 L.ptr(dec._grad_flat), int(accumulate), phase | masked,
+                                                 L.stream_of(preds)),
+                        "sat_decoder_backward")
             for hook in dec._grad_hooks:
                 hook(phase, dec)
         if dec._defer_phase2:   # phase 2 runs in dec.finish_backward()
@@ -538,4 +563,4 @@ class _DecoderFn(torch.autograd.Function):
                                 d_alphas, accumulate, masked, dec.policy)
         ctx.ws = None
         n_params = len(ctx.needs_input_grad) - 3
-        return (None, None, None) + (None,) * n_params
+        return (d_feats, None, None) + (None,) * n_params
