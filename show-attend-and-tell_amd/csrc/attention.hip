@@ -1215,12 +1215,11 @@ int sat_feature_grad_launch(const FeatureGradArgs& a, hipStream_t s) {
   SAT_REQUIRE(a.dtype == SAT_F32 || a.dtype == SAT_BF16);
   SAT_REQUIRE(a.alpha && a.dctx && a.out);
   const int fgv = a.dtype == SAT_BF16 ? 8 : 4;
-  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   // 16-byte rows: the kernel's vector loads and stores
-  SAT_REQUIRE(al16(a.dctx) && a.dctx_bs % 4 == 0 && a.dctx_ts % 4 == 0);
-  SAT_REQUIRE(al16(a.out) && a.out_ld % fgv == 0 && a.out_ld >= a.D);
-  SAT_REQUIRE(!a.addend || (al16(a.addend) && a.addend_ld % 4 == 0 && a.addend_ld >= a.D));
-  SAT_REQUIRE(!a.mean_term || (al16(a.mean_term) && a.mean_ld % 4 == 0 && a.mean_ld >= a.D));
+  SAT_REQUIRE(sat_al16(a.dctx) && a.dctx_bs % 4 == 0 && a.dctx_ts % 4 == 0);
+  SAT_REQUIRE(sat_al16(a.out) && a.out_ld % fgv == 0 && a.out_ld >= a.D);
+  SAT_REQUIRE(!a.addend || (sat_al16(a.addend) && a.addend_ld % 4 == 0 && a.addend_ld >= a.D));
+  SAT_REQUIRE(!a.mean_term || (sat_al16(a.mean_term) && a.mean_ld % 4 == 0 && a.mean_ld >= a.D));
   SAT_REQUIRE(sat_cdiv(a.D, 64 * fgv) <= 65535);   // grid.z; grid.y <= kMaxL / 32
   const dim3 grid(a.B, sat_cdiv(a.L, FGL_WAVES * FGL_LG), sat_cdiv(a.D, 64 * fgv));
   if (a.dtype == SAT_BF16) hipLaunchKernelGGL(feature_grad_kernel<bf16>, grid, dim3(FGL_WAVES * 64), 0, s, a);

@@ -27,16 +27,13 @@
 // grouping): results are bit-identical to the tile kernel (tests/test_gpu_parity.py).
 #include "sat_common.h"
 #include "sat_internal.h"
+#include "sat_lds_pipe.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void w_lds_void;
-typedef unsigned __attribute__((ext_vector_type(2))) w_u32x2;
 
 constexpr int WS_NW = 8;                 // waves per workgroup: 4 channel groups x 2 pixel halves
 constexpr int WS_NOUT = 64;              // output channels (4 groups of 16)
 constexpr int WS_MB = 7;                 // 16-pixel m-blocks per wave (112 of the item's 224 pixels)
-constexpr unsigned WS_OOB = 0x80000000u;
 
 struct WArgs {
   const bf16* x; const bf16* w; const float* bias; bf16* y;
@@ -45,12 +42,6 @@ struct WArgs {
   unsigned x_bytes, y_bytes;
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
-
-template <int N>
-__device__ __forceinline__ void w_wait_barrier_n() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // KK x KK window with PADT rows / columns of top-left padding over C input channels (3 / 64 / 1: the
 // 3x3 convs; 4 / 16 / 2: ResNet152's stem as a 4x4 conv over the 2x2 space-to-depth input);
@@ -113,8 +104,8 @@ __device__ __forceinline__ void conv_ws_kernel_body(const WArgs& a) {
       const int hy = hp / HW_, hx = hp - hy * HW_;
       const int yy = y0 + hy - PADT, xx = x0 + hx - PADT;
       const bool ok = hp < HP && (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
-      const unsigned off = ok ? (unsigned)(((((long)n * a.H + yy) * a.W + xx) * C + 8 * c) * 2) : WS_OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (w_lds_void*)(st + (d * WS_NW + w) * 1024), 16, (int)off, 0, 0, 0);
+      const unsigned off = ok ? (unsigned)(((((long)n * a.H + yy) * a.W + xx) * C + 8 * c) * 2) : kSatOOB;
+      sat_bdma16(rX, st + (d * WS_NW + w) * 1024, off);
     }
   };
   // the halo pixel of output pixel i*16 + fr under tap (kh, kw) = hp0[i] + kh * HW_ + kw
@@ -138,17 +129,17 @@ __device__ __forceinline__ void conv_ws_kernel_body(const WArgs& a) {
     if constexpr (NSTG == 3) {
       const int younger = (it + step < a.items ? NDMA : 0) + (k >= 1 ? ST : 0) + (k >= 2 ? ST : 0);
       switch (younger) {
-        case NDMA + 2 * ST: w_wait_barrier_n<NDMA + 2 * ST>(); break;
-        case NDMA + ST: w_wait_barrier_n<NDMA + ST>(); break;
-        case NDMA: w_wait_barrier_n<NDMA>(); break;
-        case 2 * ST: w_wait_barrier_n<2 * ST>(); break;
-        case ST: w_wait_barrier_n<ST>(); break;
-        default: w_wait_barrier_n<0>(); break;
+        case NDMA + 2 * ST: sat_vm_lds_barrier<NDMA + 2 * ST>(); break;
+        case NDMA + ST: sat_vm_lds_barrier<NDMA + ST>(); break;
+        case NDMA: sat_vm_lds_barrier<NDMA>(); break;
+        case 2 * ST: sat_vm_lds_barrier<2 * ST>(); break;
+        case ST: sat_vm_lds_barrier<ST>(); break;
+        default: sat_vm_lds_barrier<0>(); break;
       }
       if (it + 2 * step < a.items) stage(it + 2 * step, buf == 0 ? 2 : buf - 1);
     } else {
-      if (k >= 1) w_wait_barrier_n<ST>();
-      else w_wait_barrier_n<0>();
+      if (k >= 1) sat_vm_lds_barrier<ST>();
+      else sat_vm_lds_barrier<0>();
       if (it + step < a.items) stage(it + step, buf ^ 1);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -182,7 +173,7 @@ __device__ __forceinline__ void conv_ws_kernel_body(const WArgs& a) {
     item_origin(it, n, y0, x0);
     auto out_at = [&](int i, unsigned& off) {   // bias + act of m-block i, rounded once; its byte offset
       const int p = (ph * WS_MB + i) * 16 + fr, py = p / TW, px = p - py * TW;
-      w_u32x2 o;
+      sat_u32x2 o;
       bf16* ob = (bf16*)&o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) ob[j] = (bf16)apply_act(acc[i][j] + bias4[j], ACT);
@@ -195,12 +186,12 @@ __device__ __forceinline__ void conv_ws_kernel_body(const WArgs& a) {
 #pragma unroll
     for (int i = 0; i + 1 < WS_MB; i += 2) {
       unsigned offA, offB;
-      const w_u32x2 oa = out_at(i, offA), ob2 = out_at(i + 1, offB);
+      const sat_u32x2 oa = out_at(i, offA), ob2 = out_at(i + 1, offB);
       sat_st_pair16<0>(rY, offA, offB, oa, ob2, true, true);
     }
     if constexpr (WS_MB % 2) {
       unsigned off;
-      const w_u32x2 o = out_at(WS_MB - 1, off);
+      const sat_u32x2 o = out_at(WS_MB - 1, off);
       __builtin_amdgcn_raw_buffer_store_b64(o, rY, (int)off, 0, 0);
     }
     it += step;
@@ -215,10 +206,6 @@ __global__ __launch_bounds__(WS_NW * 64) void conv_ws_kernel(WArgs a) {
   conv_ws_kernel_body<KK, C, PADT, TR, TW, NSTG, ACT>(a);
   sat_stamp_end(a.st, t0);
 }
-
-int g_ws_cus = 0;    // CU count (queried once)
-
-inline bool wal16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <int KK, int C, int PADT, int TR, int TW, int NSTG>
 void launch_ws(int act, dim3 grid, hipStream_t s, const WArgs& a) {
@@ -244,17 +231,13 @@ int sat_conv3x3_ws_try(const SatGemm& g, hipStream_t s, int* err) {
   if (g.beta != 0.f || g.alpha != 1.f || g.partial_splits > 1) return 0;
   if (g.act != SAT_ACT_NONE && g.act != SAT_ACT_RELU) return 0;
   if (g.ldb != cv.KH * cv.KW * cv.C || g.ldc != WS_NOUT) return 0;
-  if (!wal16(g.A) || !wal16(g.B) || !wal16(g.C) || (g.bias && !wal16(g.bias))) return 0;
+  if (!sat_al16(g.A) || !sat_al16(g.B) || !sat_al16(g.C) || (g.bias && !sat_al16(g.bias))) return 0;
   const int TR = cv.W == 56 ? 4 : 2, TW = cv.W == 56 ? 56 : 112;
   if (cv.H % TR) return 0;
   const long xb = 2L * cv.N * cv.H * cv.W * cv.C, yb = 2L * cv.N * cv.H * cv.W * WS_NOUT;
   if (xb >= (1L << 31) || yb >= (1L << 31)) return 0;
-  if (g_ws_cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      return 0;
-    g_ws_cus = n;
-  }
+  const int cus = sat_cu_count();
+  if (cus == 0) return 0;
   WArgs a{};
   a.x = (const bf16*)g.A; a.w = (const bf16*)g.B; a.bias = g.bias; a.y = (bf16*)g.C;
   a.N = cv.N; a.H = cv.H; a.W = cv.W;
@@ -264,7 +247,7 @@ int sat_conv3x3_ws_try(const SatGemm& g, hipStream_t s, int* err) {
   a.x_bytes = (unsigned)xb; a.y_bytes = (unsigned)yb;
   a.st = sat_launch_stamps();
   // the stem variant (72 KB of LDS, 108 VGPRs) fits two workgroups per CU
-  const int slots = g_ws_cus * (stem ? 2 : 1);
+  const int slots = cus * (stem ? 2 : 1);
   const int grid = a.items < slots ? a.items : slots;
   if (stem) launch_ws<4, 16, 2, 2, 112, 3>(g.act, dim3(grid), s, a);
   else if (cv.W == 56) launch_ws<3, 64, 1, 4, 56, 3>(g.act, dim3(grid), s, a);

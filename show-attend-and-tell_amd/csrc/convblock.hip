@@ -31,30 +31,13 @@
 // in fp32 before the ReLU -- bit-identical to the three-launch path (tests/test_gpu_parity.py).
 #include "sat_common.h"
 #include "sat_internal.h"
-
-#include <utility>
+#include "sat_lds_pipe.h"
 
 #ifndef SAT_C2_ABL
 #define SAT_C2_ABL 0
 #endif
 
 namespace {
-
-typedef __attribute__((address_space(3))) void k_lds_void;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr unsigned K_OOB = 0x80000000u;
-
-// compile-time loop: f(std::integral_constant<int, T>) for T = 0 .. N-1 (register arrays indexed by
-// T stay static, every wait count is a literal)
-template <typename F, int... Ts>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Ts...>) {
-  (f(std::integral_constant<int, Ts>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 struct KArgs {
   const bf16* x;      // [N][IH][IW][CIN]
@@ -66,13 +49,6 @@ struct KArgs {
   unsigned x_bytes;
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
-
-template <int N>
-__device__ __forceinline__ void k_wait_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void k_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // vmem instructions one wave issues after its input DMAs A(T) (na instructions) and before the wait
 // of c1 k-tile T: the issue order is A0 B0 A1 B1 B2 .. B(PF-1) (B = nb weight loads), then per k-tile
@@ -128,8 +104,8 @@ constexpr int younger_than_a_da(int T, int KT1, int NT, int PF, int da, int nb, 
 // n-blocks, bit 6 k-major fragment layout; bit 7 the co-residency variant (one LDS activation image,
 // <= 168 VGPRs: bottleneck_kernel_share)
 // bias + ReLU of one C^T accumulator (4 consecutive channels of one pixel), rounded once to bf16
-__device__ __forceinline__ u32x2 relu_bf16x4(const f32x4& a, const float4& b) {
-  u32x2 o;
+__device__ __forceinline__ sat_u32x2 relu_bf16x4(const f32x4& a, const float4& b) {
+  sat_u32x2 o;
   bf16* ob = (bf16*)&o;
   ob[0] = (bf16)fmaxf(a[0] + b.x, 0.f);
   ob[1] = (bf16)fmaxf(a[1] + b.y, 0.f);
@@ -220,14 +196,15 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int d = w * 2 + u, r = d * 8 + (lane >> 3), c = (lane & 7) ^ (lane >> 3);
-    dsrc[u] = r < P1 ? (unsigned)(((pix_img + (long)ws * IW + r) * CIN + 8 * c) * 2) : K_OOB;
+    dsrc[u] = r < P1 ? (unsigned)(((pix_img + (long)ws * IW + r) * CIN + 8 * c) * 2) : kSatOOB;
   }
   auto dma_a = [&](int t) {
     char* st = smem + RING + (t % 3) * STG;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (k_lds_void*)(st + (w * 2 + u) * 1024), 16,
-                                               dsrc[u] == K_OOB ? (int)K_OOB : (int)(dsrc[u] + t * 128), 0, 0,
+      // (open-coded for the ablation's cache-policy operand; otherwise sat_bdma16)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (sat_lds_void*)(st + (w * 2 + u) * 1024), 16,
+                                               dsrc[u] == kSatOOB ? (int)kSatOOB : (int)(dsrc[u] + t * 128), 0, 0,
                                                (ABL & 8) ? 2 : 0);
   };
 
@@ -362,13 +339,13 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
 #pragma unroll
       for (int i = 0; i < MB; ++i) {
         const int r = i * 16 + fr;
-        u32x2 o;
+        sat_u32x2 o;
         bf16* ob = (bf16*)&o;
         ob[0] = (bf16)fmaxf(acc[i][j][0] + bv.x, 0.f);
         ob[1] = (bf16)fmaxf(acc[i][j][1] + bv.y, 0.f);
         ob[2] = (bf16)fmaxf(acc[i][j][2] + bv.z, 0.f);
         ob[3] = (bf16)fmaxf(acc[i][j][3] + bv.w, 0.f);
-        *(u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) = o;
+        *(sat_u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) = o;
       }
     }
   };
@@ -385,15 +362,15 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
   load_b(0, bq[0]);
   dma_a(1);
   load_b(1, bq[1]);
-  static_for<PF - 2>([&](auto e) { load_b(2 + decltype(e)::value, bq[2 + decltype(e)::value]); });
+  sat_static_for<PF - 2>([&](auto e) { load_b(2 + decltype(e)::value, bq[2 + decltype(e)::value]); });
   zero_acc();
-  u32x2 resv[MB][2];
+  sat_u32x2 resv[MB][2];
 
-  static_for<NT>([&](auto Tc) {
+  sat_static_for<NT>([&](auto Tc) {
     constexpr int T = decltype(Tc)::value;
     if constexpr (T < KT1) {
       // this wave's DMAs of input tile T have landed; younger: B(T), [A(T+1)], B(T+1)
-      k_wait_barrier<younger_than_a(T, KT1, NT, PF, !(ABL & 2))>();
+      sat_vm_lds_barrier<younger_than_a(T, KT1, NT, PF, !(ABL & 2))>();
       if constexpr (T + 2 < KT1) dma_a(T + 2);
     }
     if constexpr (T + PF < NT && !(ABL & 2)) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
@@ -401,12 +378,12 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
     if constexpr (T < KT1) {
       tile_u(smem + RING + (T % 3) * STG, bq[BQ]);
       if constexpr (T == KT1 - 1) {   // c1 epilogue -> X1 (the ring is read for the last time above)
-        if constexpr (SHARE) k_lds_barrier();   // every wave's last ring reads retired before X1 overwrites it
+        if constexpr (SHARE) sat_lds_barrier();   // every wave's last ring reads retired before X1 overwrites it
         if constexpr (SHARE) lds_bias(0, bias_a);
         store_planes(X1, X1PL, bias_a);
         if constexpr (SHARE) zero_row();
         zero_acc();
-        k_lds_barrier();
+        sat_lds_barrier();
       }
     } else if constexpr (T < KT1 + KT2) {
       constexpr int t = T - KT1, tap = t / (CMID / 64), pl = t % (CMID / 64);
@@ -414,11 +391,11 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
       if constexpr (pl == 0) tap_offsets(tap);
       tile_s(smem + X1 + pl * X1PL, bq[BQ]);
       if constexpr (t == KT2 - 1) {   // c2 epilogue -> X2
-        if constexpr (SHARE) k_lds_barrier();   // every wave's c2 reads of X1 retired before X2 overwrites it
+        if constexpr (SHARE) sat_lds_barrier();   // every wave's c2 reads of X1 retired before X2 overwrites it
         if constexpr (SHARE) lds_bias(CMID, bias_b);
         store_planes(X2, X2P, bias_b);
         zero_acc();
-        k_lds_barrier();
+        sat_lds_barrier();
       }
     } else {
       constexpr int t = T - KT1 - KT2, ck = t / KT3C, kt = t % KT3C;
@@ -429,7 +406,7 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) {   // rows past PO load a valid row (never stored): no branch
             const int p = min(i * 16 + fr, PO - 1), ch = ck * 256 + wn * 32 + j * 16 + 4 * fh;
-            const u32x2* rp = (const u32x2*)(a.x + (pix_img + (long)y0 * IW + p) * CIN + ch);
+            const sat_u32x2* rp = (const sat_u32x2*)(a.x + (pix_img + (long)y0 * IW + p) * CIN + ch);
             if constexpr (ABL & 8) resv[i][j] = __builtin_nontemporal_load(rp);
             else resv[i][j] = *rp;
           }
@@ -448,11 +425,11 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
             const int p = i * 16 + fr;
             const bf16* rh = (const bf16*)&resv[i][j];
             float v[4] = {acc[i][j][0] + bv.x, acc[i][j][1] + bv.y, acc[i][j][2] + bv.z, acc[i][j][3] + bv.w};
-            u32x2 o;
+            sat_u32x2 o;
             bf16* ob = (bf16*)&o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) ob[e] = (bf16)fmaxf(v[e] + (float)rh[e], 0.f);
-            u32x2* yp = (u32x2*)(a.y + (pix_img + (long)y0 * IW + p) * CIN + ch);
+            sat_u32x2* yp = (sat_u32x2*)(a.y + (pix_img + (long)y0 * IW + p) * CIN + ch);
             if constexpr (ABL & 16) {
               if (p < PO) __builtin_nontemporal_store(o, yp);
             } else {
@@ -522,14 +499,13 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
   for (int u = 0; u < NA; ++u) {
     const int d = w * NA + u, r = d * 8 + (lane >> 3), c = (lane & 7) ^ (lane >> 3), s = r / IW;
     const bool ok = r < P1 && s >= s_lo && s <= s_hi;
-    dsrc[u] = ok ? (unsigned)(((pix_img + (long)(y0 - 1) * IW + r) * CIN + 8 * c) * 2) : K_OOB;
+    dsrc[u] = ok ? (unsigned)(((pix_img + (long)(y0 - 1) * IW + r) * CIN + 8 * c) * 2) : kSatOOB;
   }
   auto dma_a = [&](int t) {
     char* st = smem + RING + (t % 3) * STG;
 #pragma unroll
     for (int u = 0; u < NA; ++u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (k_lds_void*)(st + (w * NA + u) * 1024), 16,
-                                               dsrc[u] == K_OOB ? (int)K_OOB : (int)(dsrc[u] + t * 128), 0, 0, 0);
+      sat_bdma16(rX, st + (w * NA + u) * 1024, dsrc[u] == kSatOOB ? kSatOOB : dsrc[u] + t * 128);
   };
 
   // ---- weight fragments of k-tile T: this wave's n-block of the phase (c3: of chunk ck), both 32-k halves ----
@@ -598,13 +574,13 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
       const int r = i * 16 + fr;
-      u32x2 o;
+      sat_u32x2 o;
       bf16* ob = (bf16*)&o;
       ob[0] = (bf16)fmaxf(acc[i][0] + bv.x, 0.f);
       ob[1] = (bf16)fmaxf(acc[i][1] + bv.y, 0.f);
       ob[2] = (bf16)fmaxf(acc[i][2] + bv.z, 0.f);
       ob[3] = (bf16)fmaxf(acc[i][3] + bv.w, 0.f);
-      if (r < rows) *(u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) = o;
+      if (r < rows) *(sat_u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) = o;
     }
   };
 
@@ -618,17 +594,17 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
   load_b(0, bq[0]);
   dma_a(1);
   load_b(1, bq[1]);
-  static_for<PF - 2>([&](auto e) { load_b(2 + decltype(e)::value, bq[2 + decltype(e)::value]); });
+  sat_static_for<PF - 2>([&](auto e) { load_b(2 + decltype(e)::value, bq[2 + decltype(e)::value]); });
   zero_acc();
-  u32x2 resv[MB2];
+  sat_u32x2 resv[MB2];
 
-  static_for<NT>([&](auto Tc) {
+  sat_static_for<NT>([&](auto Tc) {
     constexpr int T = decltype(Tc)::value;
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (T < KT1) {
       // this wave's DMAs of tile T have landed (every wave's after the barrier, which also retires every
       // wave's reads of stage (T + 2) % 3 before it is refilled)
-      k_wait_barrier<younger_than_a(T, KT1, NT, PF, true, 2, NA)>();
+      sat_vm_lds_barrier<younger_than_a(T, KT1, NT, PF, true, 2, NA)>();
       if constexpr (T + 2 < KT1) dma_a(T + 2);
     }
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
@@ -638,7 +614,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
       if constexpr (T == KT1 - 1) {   // c1 epilogue -> X1 (slot pixels 0 .. P1 - 1)
         store_planes(std::integral_constant<int, MB1>{}, X1, X1PL, P1, bias1);
         zero_acc();
-        k_lds_barrier();
+        sat_lds_barrier();
       }
     } else if constexpr (T < KT1 + KT2) {
       constexpr int t = T - KT1, pl = t % NPL;
@@ -647,7 +623,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
       if constexpr (t == KT2 - 1) {   // c2 epilogue -> X2 (the ring is dead: every wave passed c1's barrier)
         store_planes(std::integral_constant<int, MB2>{}, X2, X2PL, MB2 * 16, bias2);
         zero_acc();
-        k_lds_barrier();
+        sat_lds_barrier();
       }
     } else {
       constexpr int t = T - KT1 - KT2, ck = t / KT3C, kt = t % KT3C;
@@ -657,7 +633,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
 #pragma unroll
         for (int i = 0; i < MB2; ++i) {   // rows past PO load a valid row (never stored): no branch
           const int p = min(i * 16 + fr, PO - 1);
-          resv[i] = *(const u32x2*)(a.x + (pix_img + (long)y0 * IW + p) * CIN + ch);
+          resv[i] = *(const sat_u32x2*)(a.x + (pix_img + (long)y0 * IW + p) * CIN + ch);
         }
       }
       tile_u(std::integral_constant<int, MB2>{}, smem + X2 + kt * X2PL, b);
@@ -667,7 +643,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
           const int p = i * 16 + fr;
           const bf16* rh = (const bf16*)&resv[i];
           const float v[4] = {acc[i][0] + bias3.x, acc[i][1] + bias3.y, acc[i][2] + bias3.z, acc[i][3] + bias3.w};
-          u32x2 o;
+          sat_u32x2 o;
           bf16* ob = (bf16*)&o;
 #pragma unroll
           for (int e = 0; e < 4; ++e) ob[e] = (bf16)fmaxf(v[e] + (float)rh[e], 0.f);
@@ -736,8 +712,7 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
   auto dma_plane = [&](int pl) {
 #pragma unroll
     for (int u = 0; u < PPW; ++u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (k_lds_void*)(smem + pl * X1PL + dpc[u] * 1024), 16,
-                                               (int)(dsrc[u] + pl * 128), 0, 0, 0);
+      sat_bdma16(rX, smem + pl * X1PL + dpc[u] * 1024, dsrc[u] + pl * 128);
   };
   dma_plane(0);
   float4 bv[2];
@@ -752,7 +727,7 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
       for (int ks = 0; ks < 2; ++ks)
         dst[ks][j] = *(const bf16x8*)(wf + ((long)((wc * 2 + j) * KS + 2 * T + ks) * 64 + lane) * 8);
   };
-  static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
+  sat_static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
 #pragma unroll
   for (int pl = 1; pl < NPL; ++pl) dma_plane(pl);
   if (tid < NPL * 8) *(uint4*)(smem + (tid >> 3) * X1PL + P1 * ROWB + (tid & 7) * 16) = make_uint4(0, 0, 0, 0);
@@ -779,9 +754,9 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
   // prologue's fragments reused), bit 1 no MFMA, bit 2 no A fragment reads from LDS (the first read reused)
   constexpr int ABL = SAT_C2_ABL;
   bf16x8 af0[2][MB];
-  static_for<NT>([&](auto Tc) {
+  sat_static_for<NT>([&](auto Tc) {
     constexpr int T = decltype(Tc)::value, pl = T % NPL;
-    if constexpr (T < NPL) k_wait_barrier<PPW * (NPL - 1 - T)>();   // plane T (and the zero rows) in LDS
+    if constexpr (T < NPL) sat_vm_lds_barrier<PPW * (NPL - 1 - T)>();   // plane T (and the zero rows) in LDS
     if constexpr (T + PF < NT && !(ABL & 1)) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
     if constexpr (pl == 0) tap_offsets(T / NPL);
     const bf16x8 (&b)[2][2] = bq[(ABL & 1) ? T % PF : T % (PF + 1)];
@@ -883,13 +858,12 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
     const int d = w + NWV * u < NPC ? w + NWV * u : w;   // waves without another piece repeat their first (same bytes)
     const int r = d * 8 + (lane >> 3), g = (y0 - 1) * IW + r;
     dpc[u] = d;
-    dsrc[u] = r < ZR && g >= 0 ? (unsigned)((g * C + 8 * ((lane & 7) ^ (lane >> 3))) * 2) : K_OOB;
+    dsrc[u] = r < ZR && g >= 0 ? (unsigned)((g * C + 8 * ((lane & 7) ^ (lane >> 3))) * 2) : kSatOOB;
   }
   auto dma_plane = [&](int pl) {
 #pragma unroll
     for (int u = 0; u < PPW; ++u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (k_lds_void*)(smem + pl * XPL + dpc[u] * 1024), 16,
-                                               dsrc[u] == K_OOB ? (int)K_OOB : (int)(dsrc[u] + pl * 128), 0, 0, 0);
+      sat_bdma16(rX, smem + pl * XPL + dpc[u] * 1024, dsrc[u] == kSatOOB ? kSatOOB : dsrc[u] + pl * 128);
   };
   dma_plane(0);
   float4 bv[NJ];
@@ -904,7 +878,7 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
         dst[ks][j] = *(const bf16x8*)((const char*)wf + (size_t)((cb / 16 + wn * NJ + j) * KS + 2 * T + ks) * 1024 +
                                       lane_b);
   };
-  static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
+  sat_static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
 #pragma unroll
   for (int pl = 1; pl < NPL; ++pl) dma_plane(pl);
 
@@ -926,10 +900,10 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  static_for<NT>([&](auto Tc) {
+  sat_static_for<NT>([&](auto Tc) {
     constexpr int T = decltype(Tc)::value, pl = T % NPL;
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (T < NPL) k_wait_barrier<PPW * (NPL - 1 - T)>();   // plane T in LDS
+    if constexpr (T < NPL) sat_vm_lds_barrier<PPW * (NPL - 1 - T)>();   // plane T in LDS
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
     if constexpr (pl == 0) tap_offsets(T / NPL);
     const bf16x8 (&b)[2][NJ] = bq[T % (PF + 1)];
@@ -1072,14 +1046,14 @@ __device__ __forceinline__ void conv3x3_img_body(const bf16* __restrict__ x, con
       for (int ks = 0; ks < 2; ++ks)
         dst[ks][j] = *(const bf16x8*)((const char*)wf + (size_t)((cb / 16 + wr * NJ + j) * KS + 2 * T + ks) * 1024 + lane_b);
   };
-  static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
+  sat_static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
 #pragma unroll
   for (int u = 0; u < PER_T; ++u) {
     const int q = u * 512 + tid, r = q / CPP, c = q % CPP;
     if (q < P * CPP) *(uint4*)(smem + (c >> 3) * XPL + r * ROWB + 16 * ((c & 7) ^ (r & 7))) = xin[u];
   }
   if (tid < NPL * 8) *(uint4*)(smem + (tid >> 3) * XPL + ZR * ROWB + (tid & 7) * 16) = make_uint4(0, 0, 0, 0);
-  k_lds_barrier();
+  sat_lds_barrier();
 
   int offs[MB][2];
   auto tap_offsets = [&](int tap) {
@@ -1099,7 +1073,7 @@ __device__ __forceinline__ void conv3x3_img_body(const bf16* __restrict__ x, con
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  static_for<NT>([&](auto Tc) {
+  sat_static_for<NT>([&](auto Tc) {
     constexpr int T = decltype(Tc)::value, pl = T % NPL;
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
@@ -1213,14 +1187,13 @@ __device__ __forceinline__ void conv1x1_frag_body(const bf16* __restrict__ x, co
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int d = w * 2 + u, r = d * 8 + (lane >> 3), c = (lane & 7) ^ (lane >> 3);
-    dsrc[u] = r < PO ? (unsigned)(((pix0 + r) * CI + 8 * c) * 2) : K_OOB;
+    dsrc[u] = r < PO ? (unsigned)(((pix0 + r) * CI + 8 * c) * 2) : kSatOOB;
   }
   auto dma_a = [&](int t) {
     char* st = smem + (t % (DA + 1)) * STG;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (k_lds_void*)(st + (w * 2 + u) * 1024), 16,
-                                               dsrc[u] == K_OOB ? (int)K_OOB : (int)(dsrc[u] + t * 128), 0, 0, 0);
+      sat_bdma16(rX, st + (w * 2 + u) * 1024, dsrc[u] == kSatOOB ? kSatOOB : dsrc[u] + t * 128);
   };
   bf16x8 bq[PF + 1][2][NJ];
   auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) {
@@ -1244,17 +1217,17 @@ __device__ __forceinline__ void conv1x1_frag_body(const bf16* __restrict__ x, co
 
   // issue order A0 B0 A1 B1 .. (A(e) for e < DA, B(e) for e < PF, interleaved), then per k-tile after its wait
   // A(T+DA), B(T+PF): the order younger_than_a_da() counts (bias loads are older than A0 and retire first)
-  static_for<(DA > PF ? DA : PF)>([&](auto e) {
+  sat_static_for<(DA > PF ? DA : PF)>([&](auto e) {
     constexpr int E = decltype(e)::value;
     if constexpr (E < DA) dma_a(E);
     if constexpr (E < PF) load_b(E, bq[E]);
   });
 
-  static_for<NT>([&](auto Tc) {
+  sat_static_for<NT>([&](auto Tc) {
     constexpr int T = decltype(Tc)::value;
     // this wave's DMAs of tile T have landed, every wave's too after the barrier; the barrier also
     // retires every wave's reads of stage (T + 2) % 3 (tile T - 1) before it is refilled
-    k_wait_barrier<younger_than_a_da(T, NT, NT, PF, DA, 2 * NJ, 2)>();
+    sat_vm_lds_barrier<younger_than_a_da(T, NT, NT, PF, DA, 2 * NJ, 2)>();
     if constexpr (T + DA < NT) dma_a(T + DA);
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
     const bf16x8 (&b)[2][NJ] = bq[T % (PF + 1)];
@@ -1358,7 +1331,7 @@ int sat_frag_slices(int N) {
 
 extern "C" int sat_mfma_frag_layout(int N, int K, const void* src, void* dst, void* stream) {
   SAT_REQUIRE(src && dst && N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0);
-  SAT_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0);
+  SAT_REQUIRE(sat_al16(src) && sat_al16(dst));
   const long n8 = (long)N * K / 8;
   const int g = (int)((n8 + 255) / 256 < 4096 ? (n8 + 255) / 256 : 4096);
   hipLaunchKernelGGL(frag_layout_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, (bf16*)dst, N, K);

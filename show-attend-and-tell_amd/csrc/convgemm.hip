@@ -37,6 +37,7 @@
 #define SAT_SLAB_WT 1
 #endif
 #include "sat_internal.h"
+#include "sat_lds_pipe.h"
 
 namespace {
 
@@ -61,66 +62,16 @@ struct FArgs {
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-// k-major ("transposed") operand tile: 64 k-rows x 128 elements = 256-B rows, 16-B chunk ch of
-// row r stored at slot ch ^ swz(r) (cdna_hip_programming.md T10, image (b)): conflict-free for
-// ds_read_b64_tr_b16 fragment reads.
-__device__ __forceinline__ int swz256(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 // bf16 LDS epilogue images (fast_gemm_kernel RL): residual tile for ds_read_b64_tr_b16 and the
 // finished output tile, rows of BN*2 bytes; both conflict-free for their access patterns
 template <int BN> __device__ __forceinline__ int res_swz(int r) {
-  if constexpr (BN == 128) return swz256(r);
+  if constexpr (BN == 128) return sat_swz256(r);
   else return ((r >> 1) & 3) << 1;   // 128-B rows: rows r and r+2 share banks
 }
 __device__ __forceinline__ int out_swz(int r) { return ((r >> 2) & 3) << 1; }
 
-// MFMA 16x16x32 operand fragment (8 consecutive k of one row x) from a k-major tile:
-// two transposing reads of 4 k-rows x 16 columns each.
-__device__ __forceinline__ bf16x8 frag_tr(const char* tile, int kbase, int xt, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int ch = (xt >> 3) + (p >> 1);
-  const int r0 = kbase + 8 * g + q, r1 = r0 + 4;
-  const char* a0 = tile + r0 * 256 + 16 * (ch ^ swz256(r0)) + 8 * (p & 1);
-  const char* a1 = tile + r1 * 256 + 16 * (ch ^ swz256(r1)) + 8 * (p & 1);
-  const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(uintptr_t)(const void*)a0);
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(uintptr_t)(const void*)a1);
-  bf16x8 r;
-  r[0] = v0[0]; r[1] = v0[1]; r[2] = v0[2]; r[3] = v0[3];
-  r[4] = v1[0]; r[5] = v1[1]; r[6] = v1[2]; r[7] = v1[3];
-  return r;
-}
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-__device__ __forceinline__ void dma16(const void* src, char* lds_dst) {
-  __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)lds_dst, 16, 0, 0);
-}
-// select the DMA source without control flow (v_cndmask on the address, one DMA per lane)
-__device__ __forceinline__ const void* sel(bool ok, const void* p, const void* z) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)z;
-  return (const void*)(ok ? a : b);
-}
-
 // AT: A stored [K][M] (m-contiguous); BT: B stored [K][N] (n-contiguous).  Transposed operands
-// need a 128-wide tile (256-B k-rows) and M, N multiples of 8.
-// Wait until at most N of this wave's vector-memory ops are outstanding, then barrier.  Raw
-// s_barrier (not __syncthreads, whose fence would drain every in-flight LDS-DMA stage).
-template <int N>
-__device__ __forceinline__ void wait_vm_barrier() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 18) asm volatile("s_waitcnt vmcnt(18)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)\n\ts_barrier" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
+// need a 128-wide tile (256-B k-rows, sat_frag_kmajor) and M, N multiples of 8.
 // Tile configurations: BM x BN block tile, WGM x WGN waves (wave tile BM/WGM x BN/WGN).
 // RL: bf16 residual + bf16 output epilogue through LDS (128x128 / 128x64 tiles, NS = 2, N % BN == 0): the
 // residual tile is DMA'd into the free ring stage during the last k-tile, added in the MFMA
@@ -144,14 +95,9 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WGN, wn = w % WGN;
-  // XCD-aware tile order (cdna_hip_programming.md T1, bijective form): dispatch round-robins
-  // consecutive workgroups over the 8 XCDs; give each XCD a contiguous run of row-major tiles so
-  // the blocks sharing an A row-panel share one L2.
+  // XCD-aware tile order: the blocks sharing an A row-panel share one L2
   int tile = blockIdx.y * gridDim.x + blockIdx.x;
-  if (a.xcd_remap) {
-    const int nwg = gridDim.x * gridDim.y, q = nwg / 8, r = nwg % 8, x = tile % 8;
-    tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + tile / 8;
-  }
+  if (a.xcd_remap) tile = sat_xcd_tile(tile, gridDim.x * gridDim.y);
   const int m0 = (tile / gridDim.x) * BM, n0 = (tile % gridDim.x) * BN;
   const int M = a.M, N = a.N;
   const int split = blockIdx.z;
@@ -200,10 +146,10 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
 #pragma unroll
       for (int j = 0; j < A_INSTR; ++j) {
         const int r = (w * A_INSTR + j) * 4 + trow;       // k-row of the tile
-        const int ch = tslot ^ swz256(r);
+        const int ch = tslot ^ sat_swz256(r);
         const int k = k0 + r, m = m0 + 8 * ch;
         const bool ok = k < K && m + 8 <= a.a_mlim;
-        dma16(sel(ok, a.A + (long)k * a.lda + m, a.zero16), sa + (w * A_INSTR + j) * 1024);
+        sat_dma16(sat_sel(ok, a.A + (long)k * a.lda + m, a.zero16), sa + (w * A_INSTR + j) * 1024);
       }
     } else if (a.amode == 1) {   // block-uniform filter tap
       const int tap = k0 / a.Cin, ci0 = k0 - tap * a.Cin;
@@ -212,8 +158,8 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
       for (int j = 0; j < A_INSTR; ++j) {
         const int ih = a_ih[j] + kh, iw = a_iw[j] + kw;
         const bool ok = a_base[j] >= 0 && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-        const void* src = sel(ok, a.A + ((a_base[j] + (long)ih * a.W + iw) * a.Cin + ci0 + 8 * a_chunk[j]), a.zero16);
-        dma16(src, sa + (w * A_INSTR + j) * 1024);
+        const void* src = sat_sel(ok, a.A + ((a_base[j] + (long)ih * a.W + iw) * a.Cin + ci0 + 8 * a_chunk[j]), a.zero16);
+        sat_dma16(src, sa + (w * A_INSTR + j) * 1024);
       }
     } else if (a.amode == 2) {  // per-lane tap (small Cin, e.g. the padded 3->8 stem)
 #pragma unroll
@@ -228,31 +174,31 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
           ok = (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
           off = (a_base[j] + (long)ih * a.W + iw) * a.Cin + ci;
         }
-        dma16(sel(ok, a.A + off, a.zero16), sa + (w * A_INSTR + j) * 1024);
+        sat_dma16(sat_sel(ok, a.A + off, a.zero16), sa + (w * A_INSTR + j) * 1024);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < A_INSTR; ++j) {
         const int k = k0 + 8 * a_chunk[j];
         const bool ok = a_base[j] >= 0 && k < K;
-        dma16(sel(ok, a.A + a_base[j] + k, a.zero16), sa + (w * A_INSTR + j) * 1024);
+        sat_dma16(sat_sel(ok, a.A + a_base[j] + k, a.zero16), sa + (w * A_INSTR + j) * 1024);
       }
     }
     if constexpr (BT) {
 #pragma unroll
       for (int j = 0; j < B_INSTR; ++j) {
         const int r = (w * B_INSTR + j) * 4 + trow;
-        const int ch = tslot ^ swz256(r);
+        const int ch = tslot ^ sat_swz256(r);
         const int k = k0 + r, n = n0 + 8 * ch;
         const bool ok = k < K && n + 8 <= N;
-        dma16(sel(ok, a.B + (long)k * a.ldb + n, a.zero16), sb + (w * B_INSTR + j) * 1024);
+        sat_dma16(sat_sel(ok, a.B + (long)k * a.ldb + n, a.zero16), sb + (w * B_INSTR + j) * 1024);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < B_INSTR; ++j) {
         const int k = k0 + 8 * b_chunk[j];
         const bool ok = b_base[j] >= 0 && k < K;
-        dma16(sel(ok, a.B + b_base[j] + k, a.zero16), sb + (w * B_INSTR + j) * 1024);
+        sat_dma16(sat_sel(ok, a.B + b_base[j] + k, a.zero16), sb + (w * B_INSTR + j) * 1024);
       }
     }
   };
@@ -269,7 +215,7 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
         const int ins = w * (NINS / NW) + j, r = ins * RPI + lane / CPR;
         const int ch = (lane % CPR) ^ res_swz<BN>(r);
         const bool ok = m0 + r < M;
-        dma16(sel(ok, (const bf16*)a.add1 + (long)(m0 + r) * a.ld_add1 + n0 + 8 * ch, a.zero16),
+        sat_dma16(sat_sel(ok, (const bf16*)a.add1 + (long)(m0 + r) * a.ld_add1 + n0 + 8 * ch, a.zero16),
               smem + buf * STAGE + ins * 1024);
       }
     }
@@ -291,7 +237,7 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         if constexpr (AT) {
-          af[i] = frag_tr(sa, ks * 32, wm * WTM + i * 16, lane);
+          af[i] = sat_frag_kmajor(sa, ks * 32, wm * WTM + i * 16, lane);
         } else {
           const int r = wm * WTM + i * 16 + fr;
           af[i] = *(const bf16x8*)(sa + r * ROWB + 16 * ((ks * 4 + fh) ^ ((r >> 1) & 7)));
@@ -300,7 +246,7 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         if constexpr (BT) {
-          bfr[j] = frag_tr(sb, ks * 32, wn * WTN + j * 16, lane);
+          bfr[j] = sat_frag_kmajor(sb, ks * 32, wn * WTN + j * 16, lane);
         } else {
           const int r = wn * WTN + j * 16 + fr;
           bfr[j] = *(const bf16x8*)(sb + r * ROWB + 16 * ((ks * 4 + fh) ^ ((r >> 1) & 7)));
@@ -322,21 +268,21 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
   for (int kt = 0; kt < nk; ++kt) {
     const int after = min(NS - 2, nk - 1 - kt);   // stages issued after tile kt (uniform)
     if constexpr (NS >= 4) {
-      if (after >= 2) wait_vm_barrier<2 * INSTR>();
-      else if (after == 1) wait_vm_barrier<INSTR>();
-      else wait_vm_barrier<0>();
+      if (after >= 2) sat_vm_barrier<2 * INSTR>();
+      else if (after == 1) sat_vm_barrier<INSTR>();
+      else sat_vm_barrier<0>();
     } else if constexpr (NS == 3) {
-      if (after == 1) wait_vm_barrier<INSTR>();
-      else wait_vm_barrier<0>();
+      if (after == 1) sat_vm_barrier<INSTR>();
+      else sat_vm_barrier<0>();
     } else {
-      wait_vm_barrier<0>();
+      sat_vm_barrier<0>();
     }
     if (kt + NS - 1 < nk) stage((kt + NS - 1) % NS, kbeg + (kt + NS - 1) * BK);
     else if (RL && kt == nk - 1) stage_res((kt + 1) % NS);
     compute(kt % NS);
   }
   if constexpr (RL) {
-    wait_vm_barrier<0>();   // residual landed, every wave done with the ring
+    sat_vm_barrier<0>();   // residual landed, every wave done with the ring
     constexpr int ROWB2 = BN * 2, CPR = BN / 8;
     const char* rs = smem + (nk % NS) * STAGE;          // residual tile
     char* os = smem + ((nk + NS - 1) % NS) * STAGE;     // finished bf16 tile
@@ -352,7 +298,7 @@ __device__ __forceinline__ void fast_gemm_kernel_body(const FArgs& a) {
         bf16x4 r4 = bf16x4{};
         if (a.add1)
           r4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-              (lds_bf16x4*)(uintptr_t)(const void*)(rs + rq * ROWB2 + 16 * (ch ^ res_swz<BN>(rq)) + 8 * (p & 1)));
+              (sat_lds_bf16x4*)(uintptr_t)(const void*)(rs + rq * ROWB2 + 16 * (ch ^ res_swz<BN>(rq)) + 8 * (p & 1)));
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float v = apply_act(acc[i][j][r] + bcol + (float)r4[r], a.act);
@@ -494,8 +440,6 @@ __global__ __launch_bounds__(WGM * WGN * 64) void fast_gemm_kernel(FArgs a) {
   sat_stamp_end(a.st, t0);
 }
 
-__device__ __attribute__((aligned(16))) bf16 g_zero16[64];
-
 // tile configurations (ids of SatPolicy::gemm_tile)
 enum { T_AUTO = 0, T128x128W8 = 1, T128x64W8 = 2, T128x128W4 = 3, T128x256W8 = 4, T256x128W8 = 5 };
 inline int tile_bm(int t) { return t == T256x128W8 ? 256 : 128; }
@@ -529,8 +473,6 @@ void launch_tile(int t, int ns, dim3 grid, hipStream_t s, const FArgs& a) {
   }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // workgroups the atomic split-K of an fp32-output product aims for (the k-major products split on gemmsplit.hip)
 constexpr int kSplitWgs = 320;
 
@@ -556,7 +498,7 @@ int sat_fast_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
   const int force_tile = pol.gemm_tile >= T128x128W8 && pol.gemm_tile <= T256x128W8 ? pol.gemm_tile : 0;
   const int force_stages = pol.gemm_stages == 2 || pol.gemm_stages == 3 ? pol.gemm_stages : 0;
   const int res_lds = pol.gemm_epilogue == 1 ? 1 : (pol.gemm_epilogue == 2 ? 0 : 2);
-  if (!al16(g.B) || !al16(g.A)) return 0;
+  if (!sat_al16(g.B) || !sat_al16(g.A)) return 0;
   // the epilogues store through a buffer resource (32-bit offsets, sat_out_rsrc's 2 GiB cap): larger outputs take the
   // generic kernel's plain stores
   if ((long)(g.c_dtype == SAT_BF16 ? 2 : 4) * ((long)(g.M - 1) * g.ldc + g.N) >= (1L << 31)) return 0;
@@ -568,8 +510,8 @@ int sat_fast_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
   // a K tail needs B guarded per k row (k-major B) and A readable to the next 8
   if (!at && ((g.K % 8 && !(g.a_tail && bt && !conv)) || (!conv && g.lda % 8))) return 0;
   if (!bt && (g.K % 8 || g.ldb % 8)) return 0;
-  if (g.bias && !al16(g.bias)) return 0;
-  if (g.add1 && !al16(g.add1)) return 0;
+  if (g.bias && !sat_al16(g.bias)) return 0;
+  if (g.add1 && !sat_al16(g.add1)) return 0;
   const bool partial = g.partial_splits > 1;
   if (partial && (g.c_dtype != SAT_F32 || g.act != SAT_ACT_NONE || g.add1 || g.beta != 0.f || conv)) return 0;
   // skinny partial-split problems (per-step decoder GEMMs): narrow N tiles for more blocks
@@ -606,12 +548,8 @@ int sat_fast_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
   } else if (g.beta != 0.f) {
     splitk = 1;   // beta == 1 accumulate through the atomic epilogue with a single split
   }
-  static bf16* zero = nullptr;
-  if (!zero) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_zero16)) != hipSuccess) return 0;
-    zero = (bf16*)p;
-  }
+  const bf16* const zero = sat_zero_line();
+  if (!zero) return 0;
   FArgs a{};
   a.M = g.M; a.N = g.N; a.K = g.K;
   a.a_mlim = at && g.a_tail ? sat_cdiv(g.M, 8) * 8 : g.M;
@@ -651,7 +589,7 @@ int sat_fast_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
   a.st = sat_launch_stamps();
   a.res_lds = res_lds && (tcfg == T128x128W8 || tcfg == T128x64W8) && !at && !bt && a.splitk == 1 && !partial &&
               a.c_bf16 && (!g.add1 || (a.add1_bf16 && g.ld_add1 % 8 == 0)) && g.N % bn == 0 && g.ldc % 8 == 0 &&
-              al16(g.C) &&
+              sat_al16(g.C) &&
               (g.add1 || res_lds > 1) &&
               (force_stages == 0 || force_stages == 2);
   dim3 grid(sat_cdiv(g.N, bn), sat_cdiv(g.M, bm), a.splitk);

@@ -32,11 +32,9 @@
 //     fast_gemm_kernel, so both kernels give bit-identical outputs.
 #include "sat_common.h"
 #include "sat_internal.h"
+#include "sat_lds_pipe.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void p_lds_void;
-typedef __attribute__((address_space(1))) const void p_gbl_void;
 
 constexpr int PBM = 256, PBN = 128, PBK = 64, PROW = PBK * 2;   // 128-byte LDS rows
 constexpr int P_STAGE_A = PBM * PROW, P_STAGE_B = PBN * PROW, P_STAGE = P_STAGE_A + P_STAGE_B;
@@ -61,30 +59,6 @@ struct PArgs {
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
 
-// s_waitcnt vmcnt(N) + raw s_barrier (never __syncthreads: its fence would drain the DMA ring)
-template <int N>
-__device__ __forceinline__ void p_wait_barrier() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
-__device__ __forceinline__ void pdma(const void* src, char* dst) {
-  __builtin_amdgcn_global_load_lds((p_gbl_void*)src, (p_lds_void*)dst, 16, 0, 0);
-}
-// LDS-DMA through a raw buffer resource: out-of-range offsets (0x80000000) land zeros in LDS, so
-// padding taps / rows past M or N need one v_cndmask on a 32-bit offset instead of 64-bit
-// address arithmetic and a zero line.
-__device__ __forceinline__ void pbdma(__amdgpu_buffer_rsrc_t r, char* dst, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (p_lds_void*)dst, 16, (int)voff, (int)soff, 0, 0);
-}
-constexpr unsigned P_OOB = 0x80000000u;
-__device__ __forceinline__ const void* psel(bool ok, const void* p, const void* z) {
-  const uintptr_t x = (uintptr_t)p, y = (uintptr_t)z;
-  return (const void*)(ok ? x : y);
-}
-
 // NW = 8: waves 4 (M) x 2 (N), 64 x 64 per wave;  NW = 4: waves 2 x 2, 128 x 64 per wave.
 // ABL (diagnostics only, tools/pipe_ab.py): bit 0 = no MFMA, bit 1 = no in-loop DMA,
 // bit 2 = no in-loop fragment reads.
@@ -100,10 +74,7 @@ __device__ __forceinline__ void conv_pipe_kernel_body(const PArgs& a) {
   const int wm = w >> 1, wn = w & 1;
 
   int tile = blockIdx.x;
-  if (a.xcd_remap) {   // cdna_hip_programming.md T1, bijective form
-    const int nwg = gridDim.x, q = nwg / 8, r = nwg % 8, x = tile % 8;
-    tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + tile / 8;
-  }
+  if (a.xcd_remap) tile = sat_xcd_tile(tile, gridDim.x);
   const int m0 = (tile / a.tiles_n) * PBM, n0 = (tile % a.tiles_n) * PBN;
   const int M = a.M, N = a.N;
 
@@ -154,7 +125,7 @@ __device__ __forceinline__ void conv_pipe_kernel_body(const PArgs& a) {
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)a.B, (short)0, (int)a.b_bytes, 0x00020000);
   unsigned b_voff[P_BI];
 #pragma unroll
-  for (int j = 0; j < P_BI; ++j) b_voff[j] = b_ok[j] ? 2u * (unsigned)b_off[j] : P_OOB;
+  for (int j = 0; j < P_BI; ++j) b_voff[j] = b_ok[j] ? 2u * (unsigned)b_off[j] : kSatOOB;
   // part 0: the A operand, part 1: the B operand, part 2: both
   auto stage_part = [&](int buf, int part) {
     char* sa = smem + buf * P_STAGE;
@@ -164,18 +135,18 @@ __device__ __forceinline__ void conv_pipe_kernel_body(const PArgs& a) {
       for (int j = 0; j < P_AI; ++j) {
         if constexpr (BUF) {
           const bool ok = (a_ok[j] >> s_tap) & 1u;
-          pbdma(rA, sa + (w * P_AI + j) * 1024, ok ? 2u * (unsigned)(a_off[j] + s_delta) : P_OOB, 0u);
+          sat_bdma16(rA, sa + (w * P_AI + j) * 1024, ok ? 2u * (unsigned)(a_off[j] + s_delta) : kSatOOB, 0u);
         } else {
           const bool ok = (a_ok[j] >> s_tap) & 1u;
-          pdma(psel(ok, a.A + (a_off[j] + s_delta), a.zero16), sa + (w * P_AI + j) * 1024);
+          sat_dma16(sat_sel(ok, a.A + (a_off[j] + s_delta), a.zero16), sa + (w * P_AI + j) * 1024);
         }
       }
     }
     if (part != 0) {
 #pragma unroll
       for (int j = 0; j < P_BI; ++j) {
-        if constexpr (BUF) pbdma(rB, sb + (w * P_BI + j) * 1024, b_voff[j], 2u * (unsigned)s_k0);
-        else pdma(psel(b_ok[j], a.B + (b_off[j] + s_k0), a.zero16), sb + (w * P_BI + j) * 1024);
+        if constexpr (BUF) sat_bdma16(rB, sb + (w * P_BI + j) * 1024, b_voff[j], 2u * (unsigned)s_k0);
+        else sat_dma16(sat_sel(b_ok[j], a.B + (b_off[j] + s_k0), a.zero16), sb + (w * P_BI + j) * 1024);
       }
     }
   };
@@ -235,9 +206,9 @@ __device__ __forceinline__ void conv_pipe_kernel_body(const PArgs& a) {
   stage(0);
   if (nk > 1) {
     stage(1);
-    p_wait_barrier<P_INSTR>();
+    sat_vm_lds_barrier<P_INSTR>();
   } else {
-    p_wait_barrier<0>();
+    sat_vm_lds_barrier<0>();
   }
   frags(0, co0, xa, xb);
   int cur = 0;
@@ -265,8 +236,8 @@ __device__ __forceinline__ void conv_pipe_kernel_body(const PArgs& a) {
     if (t + 1 < nk) {
       // this wave's DMAs of tile t+1 have landed (t+2's stay in flight); after the barrier every
       // wave's have, and every wave's fragment reads of tile t have retired
-      if (dma) p_wait_barrier<P_INSTR>();
-      else p_wait_barrier<0>();
+      if (dma) sat_vm_lds_barrier<P_INSTR>();
+      else sat_vm_lds_barrier<0>();
       cur = cur == 2 ? 0 : cur + 1;
       if constexpr (!(ABL & 4)) frags(cur, co0, xa, xb);
     }
@@ -276,7 +247,7 @@ __device__ __forceinline__ void conv_pipe_kernel_body(const PArgs& a) {
     if (prio) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   }
-  p_wait_barrier<0>();   // ring free for the epilogue
+  sat_vm_lds_barrier<0>();   // ring free for the epilogue
 
   // ---- epilogue: fp32 (acc + bias) tile in LDS, then 16-B row segments ----
   float* ep = (float*)smem;
@@ -331,8 +302,6 @@ __global__ __launch_bounds__(NW * 64) void conv_pipe_kernel(PArgs a) {
   sat_stamp_end(a.st, t0);
 }
 
-__device__ __attribute__((aligned(16))) bf16 g_pipe_zero16[64];
-
 // DMA placement (PArgs::var): A before / B after the first MFMA half (measured best of the variants)
 constexpr int kPipeVar = 2;
 
@@ -352,8 +321,6 @@ void launch_nw(bool conv, bool res, int act, dim3 grid, hipStream_t s, const PAr
   }
 }
 
-inline bool pal16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 // Returns 1 if the problem was launched by the pipelined kernel (error code in *err), 0 otherwise.
@@ -366,8 +333,8 @@ int sat_conv_pipe_try(const SatGemm& g, hipStream_t s, int* err) {
   if (g.beta != 0.f || g.alpha != 1.f || g.partial_splits > 1) return 0;
   if (g.act != SAT_ACT_NONE && g.act != SAT_ACT_RELU) return 0;
   if (g.K % PBK || g.K < PBK || g.N % 8 || g.ldb % 8 || g.ldc % 8) return 0;
-  if (!pal16(g.A) || !pal16(g.B) || !pal16(g.C) || (g.bias && ((uintptr_t)g.bias & 3))) return 0;
-  if (g.add1 && (g.add1_dtype != SAT_BF16 || g.ld_add1 % 8 || !pal16(g.add1))) return 0;
+  if (!sat_al16(g.A) || !sat_al16(g.B) || !sat_al16(g.C) || (g.bias && ((uintptr_t)g.bias & 3))) return 0;
+  if (g.add1 && (g.add1_dtype != SAT_BF16 || g.ld_add1 % 8 || !sat_al16(g.add1))) return 0;
   const bool conv = g.conv.C > 0;
   if (conv) {
     if (g.conv.C % PBK || g.conv.KH * g.conv.KW > 32) return 0;
@@ -384,12 +351,8 @@ int sat_conv_pipe_try(const SatGemm& g, hipStream_t s, int* err) {
     if (tiles < 150 || g.N < 128 || g.add1) return 0;
     if (!(g.K >= 1024 || (g.K >= 512 && g.N >= 512))) return 0;
   }
-  static bf16* zero = nullptr;
-  if (!zero) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_pipe_zero16)) != hipSuccess) return 0;
-    zero = (bf16*)p;
-  }
+  const bf16* const zero = sat_zero_line();
+  if (!zero) return 0;
   PArgs a{};
   a.M = g.M; a.N = g.N; a.K = g.K;
   a.A = (const bf16*)g.A; a.lda = g.lda;

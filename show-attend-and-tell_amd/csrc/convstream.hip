@@ -40,14 +40,11 @@
 #endif
 
 #include "sat_internal.h"
+#include "sat_lds_pipe.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void s_lds_void;
-typedef __attribute__((address_space(3))) char s_lds_char;
-
 constexpr int S_NW = 8, S_BN = 16 * S_NW;    // 8 waves x 16 columns
-constexpr unsigned S_OOB = 0x80000000u;
 
 struct SArgs {
   int M, N, K;
@@ -66,20 +63,15 @@ struct SArgs {
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
 
-template <int N>
-__device__ __forceinline__ void s_wait_barrier_n() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-// s_waitcnt vmcnt(n) + s_barrier for a workgroup-uniform runtime n (the literal comes from a switch)
+// sat_vm_lds_barrier for a workgroup-uniform runtime n (the literal comes from a switch)
 __device__ __forceinline__ void s_wait_barrier(int n) {
   switch (n) {
-#define SW_CASE(k) case k: s_wait_barrier_n<k>(); break;
+#define SW_CASE(k) case k: sat_vm_lds_barrier<k>(); break;
     SW_CASE(1) SW_CASE(2) SW_CASE(3) SW_CASE(4) SW_CASE(5) SW_CASE(6) SW_CASE(7) SW_CASE(8) SW_CASE(9) SW_CASE(10)
     SW_CASE(11) SW_CASE(12) SW_CASE(13) SW_CASE(14) SW_CASE(15) SW_CASE(16) SW_CASE(17) SW_CASE(18) SW_CASE(19)
     SW_CASE(20) SW_CASE(21) SW_CASE(22) SW_CASE(23) SW_CASE(24)
 #undef SW_CASE
-    default: s_wait_barrier_n<0>(); break;
+    default: sat_vm_lds_barrier<0>(); break;
   }
 }
 
@@ -186,7 +178,7 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
       if constexpr (ROWB >= 256) c = (pc & ~15) | ((pc & 15) ^ (r & 15));
       else c = pc ^ ((r >> 1) & 7);
       const int m = m0 + r;
-      unsigned off = S_OOB;
+      unsigned off = kSatOOB;
       if (m < a.M) {
         long pix = m;
         if constexpr (STRIDED) {
@@ -197,7 +189,7 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
         }
         off = (unsigned)((pix * K + 8 * c) * 2);
       }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (s_lds_void*)(st + (d * S_NW + w) * 1024), 16, (int)off, 0, 0, 0);
+      sat_bdma16(rA, st + (d * S_NW + w) * 1024, off);
     }
     if constexpr (RES) {   // residual rows of this slice's columns, 16-B chunk c at slot c ^ (r & 15) in 256-B groups
 #pragma unroll
@@ -205,9 +197,8 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
         const int byte = (d * S_NW + w) * 1024 + lane * 16;
         const int r = byte / RROWB, pc = (byte % RROWB) / 16, c = (pc & ~15) | ((pc & 15) ^ (r & 15));
         const int m = m0 + r;
-        const unsigned off = m < a.M ? (unsigned)(((long)m * a.N + ns + 8 * c) * 2) : S_OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rR, (s_lds_void*)(st + TILE + (d * S_NW + w) * 1024), 16, (int)off,
-                                                 0, 0, 0);
+        const unsigned off = m < a.M ? (unsigned)(((long)m * a.N + ns + 8 * c) * 2) : kSatOOB;
+        sat_bdma16(rR, st + TILE + (d * S_NW + w) * 1024, off);
       }
     }
   };
@@ -220,7 +211,6 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
     else pc = c ^ ((r >> 1) & 7);
     return *(const bf16x8*)(base + r * ROWB + 16 * pc);
   };
-  typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
 
   int it = grp;
   if (it >= a.items) return;   // workgroup-uniform: no barrier is reached by part of a group
@@ -270,34 +260,33 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
       for (int nb = 0; nb < NB; ++nb) {
         const int lc = (wc + nb * 16 + 4 * fh) / 8;                     // logical 16-B chunk of these 8 B
         const int pc = (lc & ~15) | ((lc & 15) ^ (r & 15));
-        u32x2* slot = (u32x2*)(ro + r * RROWB + 16 * pc + 8 * (fh & 1));
+        sat_u32x2* slot = (sat_u32x2*)(ro + r * RROWB + 16 * pc + 8 * (fh & 1));
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = acc[mb][nb][j] + bias4[nb][j];
         if constexpr (RES) {
-          const u32x2 rv = *slot;
+          const sat_u32x2 rv = *slot;
           const bf16* h = (const bf16*)&rv;
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] += (float)h[j];
         }
-        u32x2 o;
+        sat_u32x2 o;
         bf16* ob = (bf16*)&o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ob[j] = (bf16)apply_act(v[j], ACT);
         *slot = o;
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: DMAs and stores stay in flight
+    sat_lds_barrier();   // LDS only: DMAs and stores stay in flight
     // the row reads are asm statements with their own lgkmcnt wait: ahead of an LDS read it can see, the compiler
     // waits for the LDS-DMAs in flight with a vmcnt(0) of its own, which drained the next items' DMAs and the last
     // items' stores in every iteration (the barrier above already orders these reads after the epilogue's writes)
-    typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-    u32x4 rows[ST];
+    sat_u32x4 rows[ST];
 #pragma unroll
     for (int p = 0; p < ST; ++p) {
       const int t = p * S_NW * 64 + tid, r = t / CPR, lc = t % CPR;
       const int pc = (lc & ~15) | ((lc & 15) ^ (r & 15));
-      asm volatile("ds_read_b128 %0, %1" : "=v"(rows[p]) : "v"((unsigned)(uintptr_t)(s_lds_char*)(ro + r * RROWB + 16 * pc)) : "memory");
+      asm volatile("ds_read_b128 %0, %1" : "=v"(rows[p]) : "v"((unsigned)(uintptr_t)(sat_lds_char*)(ro + r * RROWB + 16 * pc)) : "memory");
     }
     static_assert(ST == 1 || ST == 2 || ST == 4, "the wait below names every row register");
     if constexpr (ST == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rows[0]), "+v"(rows[1]), "+v"(rows[2]), "+v"(rows[3]) :: "memory");
@@ -306,9 +295,9 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
 #pragma unroll
     for (int p = 0; p < ST; ++p) {
       const int t = p * S_NW * 64 + tid, r = t / CPR, lc = t % CPR;
-      const u32x4 u = rows[p];
+      const sat_u32x4 u = rows[p];
       const int m = it * MT + r;
-      const unsigned off = m < a.M ? (unsigned)(((long)m * a.N + ns + 8 * lc) * 2) : S_OOB;
+      const unsigned off = m < a.M ? (unsigned)(((long)m * a.N + ns + 8 * lc) * 2) : kSatOOB;
       if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(u, rC, (int)off, 0, SAT_OUT_CPOL);
       else __builtin_amdgcn_raw_buffer_store_b128(u, rC, (int)off, 0, 0);
     }
@@ -331,10 +320,10 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
         }
       }
       // lane holds C2[m0 + (mb2 + i)*16 + fr][nb2*16 + 4 fh + j], j = 0..3: bias, ReLU, one bf16 rounding
-      u32x2 o[MB2];
+      sat_u32x2 o[MB2];
 #pragma unroll
       for (int i = 0; i < MB2; ++i) {
-        u32x2 t;
+        sat_u32x2 t;
         bf16* ob = (bf16*)&t;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ob[j] = (bf16)apply_act(acc2[i][j] + bias2[j], SAT_ACT_RELU);
@@ -351,15 +340,15 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
 #pragma unroll
         for (int i = 0; i < MB2; ++i) {
           const int r = (mb2 + i) * 16 + fr, lc = (nb2 * 16 + 4 * fh) / 8;
-          *(u32x2*)(xt + r * (N2 * 2) + 16 * (lc ^ (r & (CPR2 - 1))) + 8 * (fh & 1)) = o[i];
+          *(sat_u32x2*)(xt + r * (N2 * 2) + 16 * (lc ^ (r & (CPR2 - 1))) + 8 * (fh & 1)) = o[i];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        sat_lds_barrier();
         const int r = tid / CPR2, lc = tid % CPR2;
-        u32x4 u;   // asm, as the row reads above
+        sat_u32x4 u;   // asm, as the row reads above
         asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&v"(u) : "v"((unsigned)(uintptr_t)(s_lds_char*)(xt + r * (N2 * 2) + 16 * (lc ^ (r & (CPR2 - 1))))) : "memory");
+                     : "=&v"(u) : "v"((unsigned)(uintptr_t)(sat_lds_char*)(xt + r * (N2 * 2) + 16 * (lc ^ (r & (CPR2 - 1))))) : "memory");
         const int m = it * MT + r;
-        const unsigned off = m < a.M ? (unsigned)(((long)m * N2 + 8 * lc) * 2) : S_OOB;
+        const unsigned off = m < a.M ? (unsigned)(((long)m * N2 + 8 * lc) * 2) : kSatOOB;
         if (a.wt2) __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, SAT_OUT_CPOL);
         else __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, 0);
       } else {
@@ -370,12 +359,12 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
         const bool odd = fh & 1;
 #pragma unroll
         for (int i = 0; i < MB2; i += 2) {
-          const u32x2 send = odd ? o[i] : o[i + 1];
+          const sat_u32x2 send = odd ? o[i] : o[i + 1];
           const unsigned gx = (unsigned)__shfl_xor((int)send.x, 16, 64), gy = (unsigned)__shfl_xor((int)send.y, 16, 64);
-          const u32x4 u = odd ? u32x4{gx, gy, o[i + 1].x, o[i + 1].y} : u32x4{o[i].x, o[i].y, gx, gy};
+          const sat_u32x4 u = odd ? sat_u32x4{gx, gy, o[i + 1].x, o[i + 1].y} : sat_u32x4{o[i].x, o[i].y, gx, gy};
           const int m = it * MT + (mb2 + i + (odd ? 1 : 0)) * 16 + fr;
           const int col = nb2 * 16 + 4 * fh - (odd ? 4 : 0);
-          const unsigned off = m < a.M ? (unsigned)(((long)m * N2 + col) * 2) : S_OOB;
+          const unsigned off = m < a.M ? (unsigned)(((long)m * N2 + col) * 2) : kSatOOB;
           if (a.wt2) __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, SAT_OUT_CPOL);
           else __builtin_amdgcn_raw_buffer_store_b128(u, rC2, (int)off, 0, 0);
         }
@@ -403,19 +392,13 @@ __global__ __launch_bounds__(S_NW * 64) void conv1x1_chain_kernel(SArgs a) {
   sat_stamp_end(a.st, t0);
 }
 
-int g_stream_cus = 0;    // CU count (queried once)
-
+// CUs the persistent grids are sized for (0: the query failed)
 int stream_cus() {
-  if (g_stream_cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      return 0;
-#ifdef SAT_STREAM_CUS   // diagnostics builds: size the persistent grids for this many CUs (the rest left to a
-    n = SAT_STREAM_CUS;    // concurrent decoder)
+#ifdef SAT_STREAM_CUS   // diagnostics builds: this many CUs (the rest left to a concurrent decoder)
+  return sat_cu_count() > 0 ? SAT_STREAM_CUS : 0;
+#else
+  return sat_cu_count();
 #endif
-    g_stream_cus = n;
-  }
-  return g_stream_cus;
 }
 
 template <int KT, int MB, int NB, bool RES, bool STRIDED>
@@ -436,8 +419,6 @@ void launch_kt(bool res, bool strided, int act, dim3 grid, hipStream_t s, const 
   }
 }
 
-inline bool sal16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 // Returns 1 if the 1x1 conv was launched by the streaming kernel (error code in *err), 0 otherwise.
@@ -453,12 +434,13 @@ int sat_conv_stream_try(const SatGemm& g, hipStream_t s, int* err) {
   const int K = g.K;
   if (!(K == 64 || K == 128 || K == 256 || K == 512) || g.ldb != K) return 0;
   if (g.N % S_BN || g.ldc != g.N) return 0;
-  if (g.add1 && (g.add1_dtype != SAT_BF16 || g.ld_add1 != g.N || !sal16(g.add1))) return 0;
-  if (!sal16(g.A) || !sal16(g.B) || !sal16(g.C) || (g.bias && ((uintptr_t)g.bias & 15))) return 0;
+  if (g.add1 && (g.add1_dtype != SAT_BF16 || g.ld_add1 != g.N || !sat_al16(g.add1))) return 0;
+  if (!sat_al16(g.A) || !sat_al16(g.B) || !sat_al16(g.C) || (g.bias && ((uintptr_t)g.bias & 15))) return 0;
   const long a_bytes = 2L * cv.N * cv.H * cv.W * cv.C;
   if (a_bytes >= (1L << 31) || (long)g.M * g.N >= (1L << 31)) return 0;
   const bool strided = cv.stride != 1 || cv.OH != cv.H || cv.OW != cv.W;
-  if (stream_cus() == 0) return 0;
+  const int cus = stream_cus();
+  if (cus == 0) return 0;
   // NB = 2 (256-column slices; each A fragment read feeds two MFMAs) when N allows it, 32-row items;
   // NB = 1 (128-column slices) otherwise, 64-row items (32 at K = 512)
   const int NB = g.N % (2 * S_BN) == 0 ? 2 : 1;
@@ -471,12 +453,12 @@ int sat_conv_stream_try(const SatGemm& g, hipStream_t s, int* err) {
   const int items = sat_cdiv(g.M, MT);
   if (mode == 0) {
     // HBM-bound shapes only: enough items per workgroup to pipeline (>= ~3)
-    if ((long)items * slices < 2L * g_stream_cus) return 0;
+    if ((long)items * slices < 2L * cus) return 0;
   }
   // K = 64 with 128-column slices: two workgroups per CU fit (3 x 24 KiB of LDS, <= 128 VGPRs each)
   // and hide each other's barrier / epilogue latency; the other rings take 72-144 KiB: one per CU
   const int wpc = (K <= 64 && NB == 1) ? 2 : 1;
-  int per_slice = g_stream_cus * wpc / slices;
+  int per_slice = cus * wpc / slices;
   if (per_slice < 1) per_slice = 1;
   if (per_slice > items) per_slice = items;
   SArgs a{};
@@ -545,8 +527,8 @@ extern "C" int sat_conv1x1_chain(int64_t M, int K, int N, int N2, int dtype, con
   SatPolicyScope scope(policy);
   hipStream_t s = (hipStream_t)stream;
   const int items = chain_items(M, K, N, N2, dtype);
-  const bool ok = items > 0 && residual && sal16(x) && sal16(w) && sal16(y) && sal16(residual) && sal16(w1) && sal16(x1) &&
-                  !(bias && ((uintptr_t)bias & 15)) && !(b1 && ((uintptr_t)b1 & 15));
+  const bool ok = items > 0 && residual && sat_al16(x) && sat_al16(w) && sat_al16(y) && sat_al16(residual) &&
+                  sat_al16(w1) && sat_al16(x1) && sat_al16(bias) && sat_al16(b1);   // bias, b1: null passes
   if (!ok) {   // the two launches the chained kernel stands for, through the library's own dispatch
     SatGemm g;
     g.conv = SatConvGeom{1, 1, (int)M, K, 1, 1, 1, 0, 1, (int)M};

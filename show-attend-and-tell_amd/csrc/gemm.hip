@@ -345,7 +345,6 @@ int launch_t(const KArgs& k, int amode, int tb, int batch, hipStream_t s) {
   return tb ? launch_tiles<T, 0, true>(k, batch, s) : launch_tiles<T, 0, false>(k, batch, s);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -374,14 +373,14 @@ int sat_gemm_launch(const SatGemm& g, hipStream_t s) {
   k.cv = g.conv;
   int amode = g.conv.C > 0 ? 2 : (g.transA ? 1 : 0);
   if (amode == 2) {
-    SAT_REQUIRE(g.conv.C % vec == 0 && aligned16(g.A));
+    SAT_REQUIRE(g.conv.C % vec == 0 && sat_al16(g.A));
     SAT_REQUIRE(g.K == g.conv.KH * g.conv.KW * g.conv.C);
     SAT_REQUIRE(g.M == g.conv.N * g.conv.OH * g.conv.OW);
     k.vecA = 1;
   } else {
-    k.vecA = aligned16(g.A) && (g.lda % vec == 0) && (g.batch == 1 || g.sA % vec == 0);
+    k.vecA = sat_al16(g.A) && (g.lda % vec == 0) && (g.batch == 1 || g.sA % vec == 0);
   }
-  k.vecB = aligned16(g.B) && (g.ldb % vec == 0) && (g.batch == 1 || g.sB % vec == 0);
+  k.vecB = sat_al16(g.B) && (g.ldb % vec == 0) && (g.batch == 1 || g.sB % vec == 0);
   // split-K for skinny problems that cannot fill 256 CUs with 64x64 tiles
   k.splitk = 1;
   k.kchunk = g.K > 0 ? g.K : 1;
@@ -425,6 +424,27 @@ const SatPolicy k_default_policy{};
 }  // namespace
 
 const SatPolicy& sat_policy() { return t_policy ? *t_policy : k_default_policy; }
+
+int sat_cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      return 0;
+    return n;
+  }();
+  return cus;
+}
+
+namespace {
+__device__ __attribute__((aligned(16))) bf16 g_zero_line[64];
+}  // namespace
+const bf16* sat_zero_line() {
+  static const bf16* const zero = [] {
+    void* p = nullptr;
+    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_zero_line)) == hipSuccess ? (const bf16*)p : nullptr;
+  }();
+  return zero;
+}
 
 namespace {
 thread_local SatStamps t_stamps{};

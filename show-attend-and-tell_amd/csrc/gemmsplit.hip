@@ -27,6 +27,7 @@
 //   * XCD-aware order: the n-tiles of one (split, m-tile) panel share an XCD's L2.
 #include "sat_common.h"
 #include "sat_internal.h"
+#include "sat_lds_pipe.h"
 
 // The partial-tile hand-off without agent-scope fences: every partial is stored `sc1` (write-through, 16 B), every
 // storing wave waits vmcnt(0) before the workgroup barrier, one lane per workgroup then adds to the tile's ticket
@@ -54,12 +55,7 @@ static unsigned g_sdbg_launch = 0;
 
 namespace {
 
-typedef __attribute__((address_space(3))) void sg_lds_void;
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 sg_lds_bf16x4;
-
 constexpr int SBN = 128, SBK = 64, SNSTG = 3;
-constexpr unsigned SG_OOB = 0x80000000u;
 constexpr int kMaxSplits = 8;
 constexpr int kSplitCUs = 256;   // one workgroup per CU: a split grid stays within one round
 
@@ -94,39 +90,6 @@ struct SArgs {
   SatStamps st;
   unsigned dbg_launch;    // SAT_SPLIT_DEBUG builds: launch number
 };
-
-// k-major tile of 256-B rows: chunk slot of k-row r (conflict-free for ds_read_b64_tr_b16)
-__device__ __forceinline__ int sg_swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-
-// MFMA 16x16x32 operand fragment (8 consecutive k of column xt + lane & 15) from a k-major tile: two transposing
-// reads of 4 k-rows x 16 columns
-__device__ __forceinline__ bf16x8 sg_frag_kmajor(const char* tile, int kbase, int xt, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int ch = (xt >> 3) + (p >> 1);
-  const int r0 = kbase + 8 * g + q, r1 = r0 + 4;
-  const char* a0 = tile + r0 * 256 + 16 * (ch ^ sg_swz(r0)) + 8 * (p & 1);
-  const char* a1 = tile + r1 * 256 + 16 * (ch ^ sg_swz(r1)) + 8 * (p & 1);
-  const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((sg_lds_bf16x4*)(uintptr_t)(const void*)a0);
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((sg_lds_bf16x4*)(uintptr_t)(const void*)a1);
-  bf16x8 r;
-  r[0] = v0[0]; r[1] = v0[1]; r[2] = v0[2]; r[3] = v0[3];
-  r[4] = v1[0]; r[5] = v1[1]; r[6] = v1[2]; r[7] = v1[3];
-  return r;
-}
-
-// this wave's vector-memory ops down to the N youngest, then a raw barrier (no __syncthreads: its fence would drain
-// every LDS-DMA in flight)
-template <int N>
-__device__ __forceinline__ void sg_wait_barrier() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
-__device__ __forceinline__ void sgdma(__amdgpu_buffer_rsrc_t r, char* dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (sg_lds_void*)dst, 16, (int)voff, 0, 0, 0);
-}
 
 __device__ __forceinline__ uint4 f4u(f32x4 v) {
   return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
@@ -166,7 +129,7 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
   for (int j = 0; j < AI; ++j) {
     if constexpr (AT) {
       const int q = (w * AI + j) * 4 + (lane >> 4);   // half q >> 6 (128 m each), k-row q & 63
-      const int kr = q & 63, ch = (lane & 15) ^ sg_swz(kr);
+      const int kr = q & 63, ch = (lane & 15) ^ sat_swz256(kr);
       const int m = m0 + (q >> 6) * 128 + 8 * ch;
       a_ok[j] = m + 8 <= a.a_mlim;
       a_off[j] = m;
@@ -184,7 +147,7 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
 #pragma unroll
   for (int j = 0; j < BI; ++j) {
     if constexpr (BT) {
-      const int kr = (w * BI + j) * 4 + (lane >> 4), ch = (lane & 15) ^ sg_swz(kr);
+      const int kr = (w * BI + j) * 4 + (lane >> 4), ch = (lane & 15) ^ sat_swz256(kr);
       const int n = n0 + 8 * ch;
       b_ok[j] = n + 8 <= N;
       b_off[j] = n;
@@ -205,14 +168,14 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
       const int k = k0 + a_k[j];
       const bool ok = a_ok[j] && k < kend;
       const unsigned off = AT ? 2u * (unsigned)((long)k * a.lda + a_off[j]) : 2u * (unsigned)(a_off[j] + k);
-      sgdma(rA, sa + (w * AI + j) * 1024, ok ? off : SG_OOB);
+      sat_bdma16(rA, sa + (w * AI + j) * 1024, ok ? off : kSatOOB);
     }
 #pragma unroll
     for (int j = 0; j < BI; ++j) {
       const int k = k0 + b_k[j];
       const bool ok = b_ok[j] && k < kend;
       const unsigned off = BT ? 2u * (unsigned)((long)k * a.ldb + b_off[j]) : 2u * (unsigned)(b_off[j] + k);
-      sgdma(rB, sb + (w * BI + j) * 1024, ok ? off : SG_OOB);
+      sat_bdma16(rB, sb + (w * BI + j) * 1024, ok ? off : kSatOOB);
     }
   };
 
@@ -224,12 +187,12 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
     const char* sb = sa + G::STAGE_A;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-      if constexpr (AT) fa[i] = sg_frag_kmajor(sa + (am >> 7) * (64 * 256), h * 32, (am & 127) + i * 16, lane);
+      if constexpr (AT) fa[i] = sat_frag_kmajor(sa + (am >> 7) * (64 * 256), h * 32, (am & 127) + i * 16, lane);
       else fa[i] = *(const bf16x8*)(sa + (am + i * 16 + fr) * 128 + 16 * ((h * 4 + fh) ^ sw));
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      if constexpr (BT) fb[j] = sg_frag_kmajor(sb, h * 32, wn * G::WTN + j * 16, lane);
+      if constexpr (BT) fb[j] = sat_frag_kmajor(sb, h * 32, wn * G::WTN + j * 16, lane);
       else fb[j] = *(const bf16x8*)(sb + (wn * G::WTN + j * 16 + fr) * 128 + 16 * ((h * 4 + fh) ^ sw));
     }
   };
@@ -250,9 +213,9 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
     stage(0, kbeg);
     if (nk > 1) {
       stage(1, kbeg + SBK);
-      sg_wait_barrier<G::INSTR>();
+      sat_vm_lds_barrier<G::INSTR>();
     } else {
-      sg_wait_barrier<0>();
+      sat_vm_lds_barrier<0>();
     }
     frags(0, 0, xa, xb);
     int cur = 0;
@@ -269,8 +232,8 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
       __builtin_amdgcn_sched_barrier(0);
       if (t + 1 < nk) {
         // this wave's DMAs of tile t+1 have landed (t+2's stay in flight); after the barrier every wave's have
-        if (dma) sg_wait_barrier<G::INSTR>();
-        else sg_wait_barrier<0>();
+        if (dma) sat_vm_lds_barrier<G::INSTR>();
+        else sat_vm_lds_barrier<0>();
         cur = cur == 2 ? 0 : cur + 1;
         frags(cur, 0, xa, xb);
       }
@@ -362,7 +325,7 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
   }
 #endif
   // ---- C: the fp32 tile through LDS, 16-B row pieces (beta = 1 adds C) ----
-  sg_wait_barrier<0>();   // every wave done with the ring
+  sat_vm_lds_barrier<0>();   // every wave done with the ring
   float* ep = (float*)smem;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -406,7 +369,6 @@ __global__ __launch_bounds__(512) void split_gemm_kernel(SArgs a) {
   sat_stamp_end(a.st, t0);
 }
 
-inline bool sal16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 struct SPlan {
   int bm = 0, splits = 1, kchunk = 0, tiles_m = 0, tiles_n = 0;
@@ -463,8 +425,8 @@ bool split_eligible(const SatGemm& g) {
   // multiple of 8 (SatGemm::a_tail) against a k-major B, whose rows past K the loader skips
   if (at ? (g.M % 8 && !g.a_tail) : (g.K % 8 && !(g.a_tail && bt))) return false;
   if (!bt && g.K % 8) return false;
-  if (!sal16(g.A) || !sal16(g.B) || !sal16(g.C)) return false;
-  if (g.add1 && (g.add1_dtype != SAT_F32 || !sal16(g.add1) || g.ld_add1 % 4)) return false;
+  if (!sat_al16(g.A) || !sat_al16(g.B) || !sat_al16(g.C)) return false;
+  if (g.add1 && (g.add1_dtype != SAT_F32 || !sat_al16(g.add1) || g.ld_add1 % 4)) return false;
   // buffer offsets are 32-bit: every operand and C below 2 GiB
   const long a_bytes = at ? 2L * ((long)(g.K - 1) * g.lda + (g.a_tail ? sat_cdiv(g.M, 8) * 8 : g.M))
                           : 2L * ((long)(g.M - 1) * g.lda + sat_cdiv(g.K, 8) * 8);

@@ -23,6 +23,14 @@ typedef __bf16 bf16;
   } while (0)
 
 static inline int sat_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool sat_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Library-internal host helpers (hidden: the exported symbols are the C ABI and its dispatch, nothing more).
+// Multiprocessor (CU) count of the current device, queried once; 0 when the query fails.
+__attribute__((visibility("hidden"))) int sat_cu_count();
+// Device address of the library's one 128-byte zero line, the source of LDS-DMAs whose element lies outside the
+// operand (sat_sel, sat_lds_pipe.h); resolved once, nullptr when that fails.
+__attribute__((visibility("hidden"))) const bf16* sat_zero_line();
 
 // ---- per-call kernel selection (SatPolicy, include/sat_hip.h) ----------------
 // Every C-ABI entry point that dispatches among kernels installs its caller's policy for the duration

@@ -21,10 +21,9 @@
 // Measured and not kept (profiles/r5_s10, r5_s16): an XCD-aware workgroup order (the column blocks of one split on
 // one XCD: fewer fabric reads of A, the h GEMM 7.5 -> 9.1 us), 64-column workgroups of eight waves (half the
 // workgroups and ~60 % of the bytes moved: 7.6 -> 11.9 us per product, step 6.40 -> 6.47-6.50 ms).
-#include <utility>
-
 #include "sat_common.h"
 #include "sat_internal.h"
+#include "sat_lds_pipe.h"
 
 namespace {
 
@@ -148,7 +147,6 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_kernel(SkArgs a) {
   sat_stamp_end(a.st, t0);
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Shape / split eligibility of the skinny kernel for g (no pointer checks); fills a (pointers included) and nw.
 bool skinny_shape(const SatGemm& g, int mode, SkArgs* a, int* nw) {
@@ -188,7 +186,7 @@ bool skinny_shape(const SatGemm& g, int mode, SkArgs* a, int* nw) {
 
 bool skinny_ptrs(const SatGemm& g) {
   // + the slab stores' buffer resource takes 32-bit offsets (sat_out_rsrc's 2 GiB cap)
-  return al16(g.A) && al16(g.B) && al16(g.C) && (!g.bias || al16(g.bias)) &&
+  return sat_al16(g.A) && sat_al16(g.B) && sat_al16(g.C) && (!g.bias || sat_al16(g.bias)) &&
          4L * ((long)(g.M - 1) * g.ldc + g.N) < (1L << 31);
 }
 
@@ -312,28 +310,6 @@ __global__ __launch_bounds__(NW * 64) void head_out_kernel(HeadOutArgs a, int kw
 // MFMAs of the first quarters run while the later ones land.  Argmax partials per 64 columns (the waves' per-row
 // winners meet in LDS).
 constexpr int HO_K = 512, HO_COLS = 64, HO_BLK = 64, HO_Q = 4, HO_QB = HO_K * 2 / HO_Q;   // 256-B quarter rows
-typedef __attribute__((address_space(3))) void sk_lds_void;
-// every wave's LDS-DMAs older than its N youngest vector-memory operations have landed, then a barrier
-template <int N>
-__device__ __forceinline__ void ho_vm_barrier() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)\n\ts_barrier" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-template <typename F, int... Ts>
-__device__ __forceinline__ void sk_static_for_impl(F&& f, std::integer_sequence<int, Ts...>) {
-  (f(std::integral_constant<int, Ts>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void sk_static_for(F&& f) {
-  sk_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 template <int MB>
 __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatStamps st) {
   static_assert(MB % 2 == 0, "DMA instructions cover 4 rows: MB * 16 / 4 per quarter, a multiple of the 4 waves");
@@ -373,7 +349,7 @@ __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatSta
     for (int j = 0; j < INSTR; ++j) {
       const int r0 = 4 * (w + 4 * j), row = r0 + (lane >> 4);
       const int off = (int)(2L * ((long)min(row, a.B - 1) * a.x_ld + q * (HO_K / HO_Q) + 8 * ((lane & 15) ^ (row & 15))));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (sk_lds_void*)(quarter(q) + r0 * HO_QB), 16, off, 0, 0, 0);
+      sat_bdma16(rX, quarter(q) + r0 * HO_QB, (unsigned)off);
     }
   f32x4 acc[MB];
 #pragma unroll
@@ -386,10 +362,10 @@ __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatSta
   };
   // quarter q is waited for (the DMAs of the later quarters, INSTR each, may stay in flight) right before its k-steps;
   // within a quarter the next k-step's A fragments are read before this one's MFMAs
-  sk_static_for<HO_K / 32>([&](auto KS) {
+  sat_static_for<HO_K / 32>([&](auto KS) {
     constexpr int ks = decltype(KS)::value;
     if constexpr (ks == 0) {
-      ho_vm_barrier<(HO_Q - 1) * INSTR>();
+      sat_vm_barrier<(HO_Q - 1) * INSTR>();
       frag(0, af[0]);
     }
     if constexpr (ks + 1 < HO_K / 32 && (ks + 1) % 4 != 0) frag(ks + 1, af[(ks + 1) & 1]);
@@ -398,7 +374,7 @@ __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatSta
     for (int i = 0; i < MB; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[ks], af[ks & 1][i], acc[i], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (ks + 1 < HO_K / 32 && (ks + 1) % 4 == 0) {
-      ho_vm_barrier<(HO_Q - 1 - (ks + 1) / 4) * INSTR>();
+      sat_vm_barrier<(HO_Q - 1 - (ks + 1) / 4) * INSTR>();
       frag(ks + 1, af[(ks + 1) & 1]);
     }
   });
