@@ -41,9 +41,10 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 
 // one pass over the row: online (max, sum-exp) per thread, then a block-level merge; rows with
 // V % (16 / sizeof(T)) == 0 are read as 16-byte vectors.
+// A -inf logit (a masked vocabulary entry) adds nothing: skipped, since with m still -inf the difference is NaN.
 __device__ __forceinline__ void online_add(float& m, float& se, float x) {
   if (x > m) { se = se * expf(m - x) + 1.f; m = x; }
-  else se += expf(x - m);
+  else if (x != -INFINITY) se += expf(x - m);
 }
 
 // row r's statistics: log-sum-exp, CE term (the last step is never scored), top-1 / top-5 hits (C = number of
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const TT* __restrict__ p
     float M = red_m[0], S = red_s[0], C = red_c[0];
     for (int i = 1; i < 4; ++i) {
       const float nm = fmaxf(M, red_m[i]);
-      S = S * expf(M - nm) + red_s[i] * expf(red_m[i] - nm);
+      S = (nm == -INFINITY) ? 0.f : S * expf(M - nm) + red_s[i] * expf(red_m[i] - nm);   // as the wave merge above
       M = nm;
       C += red_c[i];
     }
