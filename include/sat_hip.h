@@ -224,6 +224,36 @@ int sat_conv1x1_chain_supported(int64_t M, int K, int N, int N2, int dtype, cons
 int sat_conv1x1_chain(int64_t M, int K, int N, int N2, int dtype, const void* x, const void* w, const float* bias,
                       const void* residual, void* y, const void* w1, const float* b1, void* x1,
                       const SatPolicy* policy, void* stream);
+/* The c3 of a stage's first bottleneck with its projection shortcut computed inside the launch (ResNet152 layer1 /
+ * layer2 block 0): y [M,N] = relu(x [M,K] . w [N,K]^T + bias + bf16(xin_m . wp [N,Kp]^T + bp)), where xin
+ * NHWC [n,H,W,Kp] is the block's input and row m = (img, oh, ow) reads its pixel (img, oh * stride, ow * stride),
+ * OH = (H - 1) / stride + 1, M = n * OH * OW.  The downsample conv's output is formed in registers from xin's tile
+ * (csrc/convstream.hip) and never written.  With N2 > 0 the launch also computes the next bottleneck's c1 as
+ * sat_conv1x1_chain does: x1 [M,N2] = relu(y . w1 [N2,N]^T + b1); N2 = 0: w1, b1, x1 are ignored.  Bit-identical to
+ * the sat_conv2d_nhwc launches (downsample, then c3 with residual, then c1).
+ * _supported: 1 if a projection kernel takes the shape -- bf16, (K, N, Kp, stride, N2) one of (64, 256, 64, 1, 0),
+ * (64, 256, 64, 1, 64), (128, 512, 256, 2, 0), M * N < 2^31 -- under the policy's conv_stream as for sat_conv2d_nhwc's
+ * stream kernel (N2 = 0) or sat_conv1x1_chain (N2 > 0).
+ * sat_conv1x1_proj has no second path: it fails with an invalid-argument code unless _supported, xin is under
+ * 2 GiB and every pointer is 16-byte aligned; the caller then issues the downsample launch itself. */
+int sat_conv1x1_proj_supported(int64_t M, int K, int N, int Kp, int stride, int N2, int dtype, const SatPolicy* policy);
+int sat_conv1x1_proj(int n, int H, int W, int stride, int K, int N, int Kp, int N2, int dtype, const void* x,
+                     const void* w, const float* bias, const void* xin, const void* wp, const float* bp, void* y,
+                     const void* w1, const float* b1, void* x1, const SatPolicy* policy, void* stream);
+/* ResNet152's stem as ONE launch: the conv (+ folded BatchNorm + ReLU) and the MaxPool2d that follows it
+ * (encoder.py:13-17 through torchvision: conv1, bn1, relu, maxpool).  g, Cout, x, w, bias, relu as for
+ * sat_conv2d_nhwc; y NHWC [N, OH / 2, OW / 2, Cout] is the pooled tensor -- the conv's own output is never written.
+ * Bit-identical to sat_conv2d_nhwc followed by sat_maxpool2d_nhwc.
+ * _supported: 1 for bf16, relu, the 4x4 / stride 1 / pad 2 stem over the 16-channel space-to-depth input at width 112
+ * (OH = H even, OW = W), Cout 64, pool (3, 2, 1), input and conv output under 2 GiB, and a policy that leaves the
+ * weight-stationary conv kernel on (conv3x3_ws != 1).
+ * sat_conv_stem_pool has no second path: it fails with an invalid-argument code unless _supported and every pointer
+ * is 16-byte aligned; the caller then issues the conv and the pool itself. */
+int sat_conv_stem_pool_supported(const SatConvGeom* g, int Cout, int dtype, int relu, int pool_k, int pool_stride,
+                                 int pool_pad, const SatPolicy* policy);
+int sat_conv_stem_pool(const SatConvGeom* g, int Cout, int dtype, const void* x, const void* w, const float* bias,
+                       int relu, int pool_k, int pool_stride, int pool_pad, void* y, const SatPolicy* policy,
+                       void* stream);
 /* MaxPool2d (floor mode, -inf padding) on NHWC. */
 int sat_maxpool2d_nhwc(int N, int H, int W, int C, int k, int stride, int pad, int dtype,
                        const void* x, void* y, int OH, int OW, void* stream);

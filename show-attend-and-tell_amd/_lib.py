@@ -99,6 +99,15 @@ _SIGNATURES = [
     ("sat_conv1x1_chain_supported", c_int, [c_int64, c_int, c_int, c_int, c_int, ctypes.POINTER(SatPolicy)]),
     ("sat_conv1x1_chain", c_int, [c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(SatPolicy), c_void_p]),
+    ("sat_conv1x1_proj_supported", c_int, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           ctypes.POINTER(SatPolicy)]),
+    ("sat_conv1x1_proj", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 ctypes.POINTER(SatPolicy), c_void_p]),
+    ("sat_conv_stem_pool_supported", c_int, [ctypes.POINTER(SatConvGeom), c_int, c_int, c_int, c_int, c_int, c_int,
+                                             ctypes.POINTER(SatPolicy)]),
+    ("sat_conv_stem_pool", c_int, [ctypes.POINTER(SatConvGeom), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_int, c_int, c_int, c_void_p, ctypes.POINTER(SatPolicy), c_void_p]),
     ("sat_maxpool2d_nhwc", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_int, c_int, c_void_p]),
     ("sat_attention_forward", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -33,6 +33,12 @@
 //     the finished output tile is the A operand of the NEXT bottleneck's c1 (weights register-stationary like B),
 //     computed beside the whole-row stores, so the c3's output is not read back for it: (K, N -> N2) = (64, 256 -> 64),
 //     (64, 256 -> 128), (128, 512 -> 128), both outputs bit-identical to the two launches.
+//   * projection form (conv1x1_proj_kernel, sat_conv1x1_proj): the c3 of a stage's first bottleneck, whose residual is
+//     the downsample conv of the block input.  The wave also keeps its columns of the downsample weights in registers,
+//     the stage holds the block input's tile (MT x Kp, strided source for layer2) in place of the residual tile, and
+//     the residual bf16(accP + biasP) is formed in registers -- the downsample launch's arithmetic -- so its output is
+//     neither written nor read: (K, N, Kp, stride) = (64, 256, 64, 1) plain and chained, (128, 512, 256, 2) plain,
+//     bit-identical to the separate launches.
 #include "sat_common.h"
 
 #ifndef SAT_STREAM_WT_BYTES
@@ -60,6 +66,11 @@ struct SArgs {
   // output tile while it is still in LDS (N2 is a template parameter)
   const bf16* B2; const float* bias2; bf16* C2;
   int wt2;                           // write-through stores of C2
+  // projection mode: the residual is the block's downsample conv, res[M, N] = bf16(P . BP[N, KP]^T + biasP), formed in
+  // registers from the block input's tile (P: NHWC [*, pH, pW, KP], pixel (n, oh * pstride, ow * pstride) for row m)
+  const bf16* P; const bf16* BP; const float* biasP;
+  int pH, pW, pstride, pOH, pOW;
+  unsigned p_bytes;
   SatStamps st;                      // in-kernel launch timestamps (SatPolicy::stamps)
 };
 
@@ -77,21 +88,28 @@ __device__ __forceinline__ void s_wait_barrier(int n) {
 
 // KT = K / 32 k-steps, MB = 16-row m-blocks per item (MT = 16 * MB rows), NB = 16-column n-blocks
 // per wave (the workgroup's slice is 128 * NB columns), N2B = 16-column n-blocks of the chained c1's output
-// (0: no chain; 4 or 8: the slice is the whole row, N = 128 * NB, and is the chained product's K)
-template <int KT, int MB, int NB, bool RES, int ACT, bool STRIDED, int N2B = 0>
+// (0: no chain; 4 or 8: the slice is the whole row, N = 128 * NB, and is the chained product's K), KTP = KP / 32
+// k-steps of the projected residual (0: none; the residual is then RES's tensor), PSTR: its input is strided
+template <int KT, int MB, int NB, bool RES, int ACT, bool STRIDED, int N2B = 0, int KTP = 0, bool PSTR = false>
 __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
   constexpr int K = KT * 32, MT = MB * 16, ROWB = K * 2;
+  constexpr bool PROJ = KTP > 0;
+  static_assert(!(PROJ && RES), "the projected residual replaces the residual tensor");
+  constexpr int KP = KTP * 32, PROWB = PROJ ? KP * 2 : 128;   // block-input row bytes
+  constexpr int PTILE = PROJ ? MT * PROWB : 0;               // block-input tile bytes, behind the R/O tile
   constexpr int SN = S_BN * NB, RROWB = SN * 2;            // slice columns, residual row bytes
   constexpr int TILE = MT * ROWB;                           // A tile bytes
   constexpr int RTILE = MT * RROWB;                          // residual-in / output-out tile bytes
-  constexpr int STG = TILE + RTILE;                         // one LDS stage
+  constexpr int STG = TILE + RTILE + PTILE;                 // one LDS stage
   constexpr int NSTG = 3;                                   // items i, i+1 (landing), i+2 (issued)
   static_assert(NSTG * STG <= 160 * 1024, "the ring must fit in LDS");
   constexpr int DMA_A = TILE / (S_NW * 64 * 16);            // 16-B DMAs per lane per item
   constexpr int DMA_R = RTILE / (S_NW * 64 * 16);
   static_assert(DMA_A * S_NW * 64 * 16 == TILE && DMA_R * S_NW * 64 * 16 == RTILE, "whole 8 KiB rounds");
   constexpr int ST = RTILE / (S_NW * 64 * 16);              // 16-B row-segment stores per lane per item
-  constexpr int DMA_N = DMA_A + (RES ? DMA_R : 0);
+  constexpr int DMA_P = PTILE / (S_NW * 64 * 16);
+  static_assert(DMA_P * S_NW * 64 * 16 == PTILE, "whole 8 KiB rounds");
+  constexpr int DMA_N = DMA_A + (RES ? DMA_R : 0) + DMA_P;
   constexpr int CPR = RROWB / 16;                           // 16-B chunks per output row
   // chained c1: wave w computes n-block w of all MB m-blocks (N2 = 128) or n-block w % 4 of m-half w / 4 (N2 = 64);
   // the output tile leaves as whole rows through LDS where it fits, else m-blocks in pairs as 16-B stores
@@ -131,6 +149,19 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
   for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
     for (int j = 0; j < 4; ++j) bias4[nb][j] = a.bias ? a.bias[ns + wc + nb * 16 + 4 * fh + j] : 0.f;
+  // projected residual: this wave's columns of BP for all of KP and their bias, registers like bq / bias4
+  bf16x8 pq[PROJ ? KTP : 1][NB];
+  float biasp4[NB][4];
+  if constexpr (PROJ) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const bf16* bp = a.BP + (long)(ns + wc + nb * 16 + fr) * KP + 8 * fh;
+#pragma unroll
+      for (int ks = 0; ks < KTP; ++ks) pq[ks][nb] = *(const bf16x8*)(bp + 32 * ks);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) biasp4[nb][j] = a.biasP ? a.biasP[ns + wc + nb * 16 + 4 * fh + j] : 0.f;
+    }
+  }
   // chained c1: this wave's 16 rows of B2 for all of its K (= N), registers for the whole kernel like bq
   const int nb2 = N2B == 4 ? (w & 3) : w, mb2 = N2B == 4 ? (w >> 2) * MB2 : 0;
   bf16x8 wq[KT2 > 0 && N2B ? KT2 : 1];
@@ -147,12 +178,23 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
     for (int ks = 0; ks < KT2; ++ks) asm volatile("" ::"v"(wq[ks]));
 #pragma unroll
     for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bias2[j]));
+  }
+  if constexpr (N2B > 0 || PROJ) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
       for (int ks = 0; ks < KT; ++ks) asm volatile("" ::"v"(bq[ks][nb]));
 #pragma unroll
       for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bias4[nb][j]));
+    }
+  }
+  if constexpr (PROJ) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+      for (int ks = 0; ks < KTP; ++ks) asm volatile("" ::"v"(pq[ks][nb]));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(biasp4[nb][j]));
     }
   }
 
@@ -163,6 +205,8 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
       __builtin_amdgcn_make_buffer_rsrc((void*)(RES ? a.res : a.C), (short)0, (int)c_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rC2 = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(N2B ? a.C2 : a.C), (short)0, (int)(N2B ? (unsigned)((long)a.M * N2 * 2) : c_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(PROJ ? a.P : a.A), (short)0, (int)(PROJ ? a.p_bytes : a.a_bytes), 0x00020000);
 
   // Every global read of the loop is an LDS-DMA (A tile and residual tile of the next item), so the
   // only vmcnt waits are the counted ones below; rows >= M read zeros through out-of-range buffer
@@ -201,6 +245,29 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
         sat_bdma16(rR, st + TILE + (d * S_NW + w) * 1024, off);
       }
     }
+    if constexpr (PROJ) {   // the block input's rows of this item, the A tile's swizzle at its own row length
+#pragma unroll
+      for (int d = 0; d < DMA_P; ++d) {
+        const int byte = (d * S_NW + w) * 1024 + lane * 16;
+        const int r = byte / PROWB, pc = (byte % PROWB) / 16;
+        int c;
+        if constexpr (PROWB >= 256) c = (pc & ~15) | ((pc & 15) ^ (r & 15));
+        else c = pc ^ ((r >> 1) & 7);
+        const int m = m0 + r;
+        unsigned off = kSatOOB;
+        if (m < a.M) {
+          long pix = m;
+          if constexpr (PSTR) {
+            const int ohw = a.pOH * a.pOW;
+            const int n = m / ohw, rem = m - n * ohw;
+            const int oh = rem / a.pOW, ow = rem - oh * a.pOW;
+            pix = ((long)n * a.pH + oh * a.pstride) * a.pW + ow * a.pstride;
+          }
+          off = (unsigned)((pix * KP + 8 * c) * 2);
+        }
+        sat_bdma16(rP, st + TILE + RTILE + (d * S_NW + w) * 1024, off);
+      }
+    }
   };
 
   // A fragment: row mb*16 + fr, logical chunk 4 ks + fh
@@ -210,6 +277,14 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
     if constexpr (ROWB >= 256) pc = (c & ~15) | ((c & 15) ^ (r & 15));
     else pc = c ^ ((r >> 1) & 7);
     return *(const bf16x8*)(base + r * ROWB + 16 * pc);
+  };
+  // block-input fragment: row mb*16 + fr, logical chunk 4 ks + fh of the P tile
+  auto pfrag = [&](const char* pbase, int mb, int ks) {
+    const int r = mb * 16 + fr, c = ks * 4 + fh;
+    int pc;
+    if constexpr (PROWB >= 256) pc = (c & ~15) | ((c & 15) ^ (r & 15));
+    else pc = c ^ ((r >> 1) & 7);
+    return *(const bf16x8*)(pbase + r * PROWB + 16 * pc);
   };
 
   int it = grp;
@@ -228,6 +303,37 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
     if (nxt2 < a.items) stage(nxt2, buf == 0 ? 2 : buf - 1);
     __builtin_amdgcn_sched_barrier(0);
     const char* base = smem + buf * STG;
+    // projected residual first: the downsample conv's arithmetic (k-steps ascending, one accumulator per output,
+    // bias, one bf16 rounding), kept packed -- 2 registers per 4 outputs -- until the epilogue adds it
+    sat_u32x2 rproj[PROJ ? MB : 1][NB];
+    if constexpr (PROJ) {
+      const char* pbase = base + TILE + RTILE;
+      f32x4 accp[MB][NB];
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) accp[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KTP; ++ks) {
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) {
+          const bf16x8 pf = pfrag(pbase, mb, ks);
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+            accp[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pq[ks][nb], pf, accp[mb][nb], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          sat_u32x2 t;
+          bf16* tb = (bf16*)&t;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) tb[j] = (bf16)apply_act(accp[mb][nb][j] + biasp4[nb][j], SAT_ACT_NONE);
+          rproj[mb][nb] = t;
+        }
+    }
     f32x4 acc[MB][NB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
@@ -267,6 +373,11 @@ __device__ __forceinline__ void conv1x1_stream_kernel_body(const SArgs& a) {
         if constexpr (RES) {
           const sat_u32x2 rv = *slot;
           const bf16* h = (const bf16*)&rv;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] += (float)h[j];
+        }
+        if constexpr (PROJ) {
+          const bf16* h = (const bf16*)&rproj[mb][nb];
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] += (float)h[j];
         }
@@ -389,6 +500,15 @@ template <int KT, int MB, int NB, int N2B>
 __global__ __launch_bounds__(S_NW * 64) void conv1x1_chain_kernel(SArgs a) {
   const SatStampT0 t0 = sat_stamp_begin(a.st);
   conv1x1_stream_kernel_body<KT, MB, NB, true, SAT_ACT_RELU, false, N2B>(a);
+  sat_stamp_end(a.st, t0);
+}
+
+// the projection forms (a stage's first bottleneck: c3 + ReLU with the downsample conv of the block input as the
+// residual, computed in registers), plain (N2B = 0) or chained
+template <int KT, int MB, int NB, int N2B, int KTP, bool PSTR>
+__global__ __launch_bounds__(S_NW * 64) void conv1x1_proj_kernel(SArgs a) {
+  const SatStampT0 t0 = sat_stamp_begin(a.st);
+  conv1x1_stream_kernel_body<KT, MB, NB, false, SAT_ACT_RELU, false, N2B, KTP, PSTR>(a);
   sat_stamp_end(a.st, t0);
 }
 
@@ -563,5 +683,86 @@ extern "C" int sat_conv1x1_chain(int64_t M, int K, int N, int N2, int dtype, con
   if (K == 64 && N2 == 64) hipLaunchKernelGGL((conv1x1_chain_kernel<2, 4, 2, 4>), grid, block, 0, s, a);
   else if (K == 64) hipLaunchKernelGGL((conv1x1_chain_kernel<2, 4, 2, 8>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((conv1x1_chain_kernel<4, 2, 4, 8>), grid, block, 0, s, a);
+  return (int)hipGetLastError();
+}
+
+// ---- projection forms: the stage's first bottleneck, its downsample conv computed inside the c3 launch ----
+namespace {
+
+// the instantiations: (K, N, KP, stride, N2) = (64, 256, 64, 1, 0 | 64) [ResNet152 layer1 block 0, plain and chained
+// into block 1's c1], (128, 512, 256, 2, 0) [layer2 block 0]; 0 = none, else the item count.  The chained
+// (128, 512 -> 128) kernel holds 254 VGPRs without the 64 of the downsample weights: it keeps its separate launch.
+int proj_items(long M, int K, int N, int KP, int stride, int N2, int dtype) {
+  if (dtype != SAT_BF16 || M <= 0) return 0;
+  const bool l1 = K == 64 && N == 256 && KP == 64 && stride == 1 && (N2 == 0 || N2 == 64);
+  const bool l2 = K == 128 && N == 512 && KP == 256 && stride == 2 && N2 == 0;
+  if (!l1 && !l2) return 0;
+  if (M * N >= (1L << 31)) return 0;   // 32-bit element / buffer offsets
+  if (N2 > 0) return chain_items(M, K, N, N2, dtype);
+  const int mode = sat_policy().conv_stream;
+  if (mode == 1) return 0;
+  const int cus = stream_cus();
+  if (cus == 0) return 0;
+  const int items = sat_cdiv(M, l1 ? 64 : 32), slices = N / (2 * S_BN);
+  if (mode == 0 && (long)items * slices < 2L * cus) return 0;   // sat_conv_stream_try's rule
+  return items;
+}
+
+}  // namespace
+
+extern "C" int sat_conv1x1_proj_supported(int64_t M, int K, int N, int Kp, int stride, int N2, int dtype,
+                                          const SatPolicy* policy) {
+  SatPolicyScope scope(policy);
+  return proj_items(M, K, N, Kp, stride, N2, dtype) > 0;
+}
+
+extern "C" int sat_conv1x1_proj(int n, int H, int W, int stride, int K, int N, int Kp, int N2, int dtype,
+                                const void* x, const void* w, const float* bias, const void* xin, const void* wp,
+                                const float* bp, void* y, const void* w1, const float* b1, void* x1,
+                                const SatPolicy* policy, void* stream) {
+  SAT_REQUIRE(n > 0 && H > 0 && W > 0 && stride > 0 && K > 0 && N > 0 && Kp > 0 && N2 >= 0 && x && w && xin && wp && y);
+  SAT_REQUIRE(N2 == 0 || (w1 && x1));
+  SatPolicyScope scope(policy);
+  hipStream_t s = (hipStream_t)stream;
+  const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  const long M = (long)n * OH * OW, p_bytes = 2L * n * H * W * Kp;
+  const int items = M < (1L << 31) ? proj_items(M, K, N, Kp, stride, N2, dtype) : 0;
+  // no second path here: the caller issues the downsample launch itself where this one does not apply
+  SAT_REQUIRE(items > 0 && p_bytes < (1L << 31));
+  SAT_REQUIRE(sat_al16(x) && sat_al16(w) && sat_al16(xin) && sat_al16(wp) && sat_al16(y) && sat_al16(bias) &&
+              sat_al16(bp) && sat_al16(w1) && sat_al16(x1) && sat_al16(b1));   // null passes
+  const int cus = stream_cus();
+  SArgs a{};
+  a.M = (int)M; a.N = N; a.K = K;
+  a.A = (const bf16*)x; a.B = (const bf16*)w; a.C = (bf16*)y;
+  a.bias = bias;
+  a.H = 1; a.W = (int)M; a.Cin = K; a.stride = 1; a.OH = 1; a.OW = (int)M;
+  a.a_bytes = (unsigned)(2L * M * K);
+  a.P = (const bf16*)xin; a.BP = (const bf16*)wp; a.biasP = bp;
+  a.pH = H; a.pW = W; a.pstride = stride; a.pOH = OH; a.pOW = OW;
+  a.p_bytes = (unsigned)p_bytes;
+  a.wt = 2L * M * N <= (long)SAT_STREAM_WT_BYTES;
+  a.items = items;
+  const dim3 block(S_NW * 64);
+  if (N2 > 0) {   // sat_conv1x1_chain's launch
+    a.slices = 1; a.per_slice = cus < items ? cus : items;
+    a.xcd_group = 0;
+    a.B2 = (const bf16*)w1; a.bias2 = b1; a.C2 = (bf16*)x1;
+    a.wt2 = N2 < S_BN || 2L * M * N2 <= (long)SAT_STREAM_WT_BYTES;
+    a.st = sat_launch_stamps();
+    hipLaunchKernelGGL((conv1x1_proj_kernel<2, 4, 2, 4, 2, false>), dim3(a.per_slice), block, 0, s, a);
+    return (int)hipGetLastError();
+  }
+  // sat_conv_stream_try's launch of the same c3 (256-column slices, one workgroup per CU)
+  const int slices = N / (2 * S_BN);
+  int per_slice = cus / slices;
+  if (per_slice < 1) per_slice = 1;
+  if (per_slice > items) per_slice = items;
+  a.slices = slices; a.per_slice = per_slice;
+  a.xcd_group = (per_slice * slices) % (8 * slices) == 0 && per_slice % 8 == 0;
+  a.st = sat_launch_stamps();
+  const dim3 grid(per_slice * slices);
+  if (K == 64) hipLaunchKernelGGL((conv1x1_proj_kernel<2, 4, 2, 0, 2, false>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((conv1x1_proj_kernel<4, 2, 2, 0, 8, true>), grid, block, 0, s, a);
   return (int)hipGetLastError();
 }

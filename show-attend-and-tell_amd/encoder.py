@@ -13,7 +13,10 @@ activations:
     (sat_conv2d_nhwc): M = B*OH*OW, N = Cout, K = KH*KW*Cin;
   * in ResNet152's layer1 a block's c3 launch also computes the next block's c1 from its
     output tile while that is still on chip (ops.conv1x1_chain; ``Encoder.chain_c1``);
-  * MaxPool2d is a streaming NHWC kernel;
+  * at the trunk's entry no tensor is written only to be read straight back: ResNet152's stem conv and its max
+    pool are one launch (ops.conv_stem_pool; ``Encoder.stem_pool``), and the projection shortcut of layer1's and
+    layer2's first block is computed inside that block's c3 launch (ops.ProjectedResidual; ``proj_l1``, ``proj_l2``);
+  * every other MaxPool2d is a streaming NHWC kernel;
   * the image is converted once to NHWC with channels zero-padded 3 -> 8 so the
     first conv loads 16-byte vectors (VGG19); for ResNet152 it is converted to a
     2x2 space-to-depth layout instead ([H/2, W/2, 16], 12 real channels) and the
@@ -176,6 +179,14 @@ class Encoder(nn.Module):
         # (A/B, tests).  Layer2 (128) is off: its chained kernel is faster than the two launches on its own but
         # slows the overlapped train step (5.95 vs 5.90 ms)
         self.chain_c1 = {64}
+        # ResNet152's stem conv and the max pool behind it as ONE launch that never writes the 112 x 112 tensor
+        # (ops.conv_stem_pool, csrc/conv3x3ws.hip), when both are in the forward's slice.  False = conv, then pool
+        self.stem_pool = True
+        # the projection shortcut of layer1's / layer2's first block computed inside its c3 launch from the block
+        # input's tile (ops.ProjectedResidual, csrc/convstream.hip): no downsample launch, and its output is neither
+        # written nor read back.  False = the downsample conv its own launch (A/B, tests)
+        self.proj_l1 = True
+        self.proj_l2 = True
         # per-call kernel selection for the conv launches (sat_amd.Policy / SatPolicy; None = the library's
         # defaults): A/B measurements and tests only
         self.policy = None
@@ -200,6 +211,19 @@ class Encoder(nn.Module):
         w, b, s, p = f
         return self._launch((x, w, b, s, p, relu, residual, out_hw), ops.conv2d_nhwc, x, w, b, s, p, relu,
                             residual=residual, out_hw=out_hw)
+
+    def _stem(self, y, plan, stop, out_hw):
+        """The space-to-depth stem on its input ``y`` and the rest of the plan up to ``stop``.  The pool step joins the
+        stem's launch where ops.conv_stem_pool runs both; the stem keeps its one bench-hook record either way (the
+        pool never had one)."""
+        w, b, s, p = plan[0][1]
+        pool = plan[1][1:] if len(plan) > 1 and plan[1][0] == "pool" else None
+        if self.stem_pool and pool is not None and stop >= 2 \
+                and ops.conv_stem_pool_supported(y, w, s, p, True, pool, out_hw, self.policy):
+            y = self._launch((y, w, b, s, p, True, None, out_hw), ops.conv_stem_pool, y, w, b, s, p, True, pool,
+                             out_hw=out_hw)
+            return self._run_plan(y, plan, stop, 2)
+        return self._run_plan(self._conv(y, plan[0][1], True, out_hw=out_hw), plan, stop)
 
     def _frag_conv(self, kind, fn, x, f, *extra):
         """A half-image fragment-weight conv launch (csrc/convblock.hip), with the bench's hooks."""
@@ -324,7 +348,7 @@ class Encoder(nn.Module):
                 raise ValueError("Encoder: packed images enter at plan step 0")
             if plan[0][0] == "stem_s2d":
                 y = ops.images_to_input(x, L.IMG_S2D16, dtype)
-                y = self._conv(y, plan[0][1], True, out_hw=(y.shape[1], y.shape[2]))
+                return self._stem(y, plan, stop, (y.shape[1], y.shape[2]))
             else:
                 y = ops.images_to_input(x, L.IMG_NHWC, dtype, c_pad=IN_PAD)
             return self._run_plan(y, plan, stop)
@@ -332,8 +356,7 @@ class Encoder(nn.Module):
             return self._run_plan(x, plan, stop, start)
         H, W = x.shape[2], x.shape[3]
         if plan[0][0] == "stem_s2d" and H % 2 == 0 and W % 2 == 0:
-            y = ops.nchw_to_s2d(x, dtype)
-            y = self._conv(y, plan[0][1], True, out_hw=(H // 2, W // 2))
+            return self._stem(ops.nchw_to_s2d(x, dtype), plan, stop, (H // 2, W // 2))
         elif plan[0][0] == "stem_s2d":   # odd image sizes: the stem on the 8-channel layout
             y = self._conv(ops.nchw_to_nhwc(x, IN_PAD, dtype), plan[0][2], True)
         else:
@@ -388,12 +411,29 @@ class Encoder(nn.Module):
             return None
         return c1n
 
-    def _absorbed(self, y, f):
-        """The bench hooks of a c1 launch the previous block's chained c3 already computed: its record in launch
-        order, an empty event pair and one launch-policy slot, so per-launch tables keep their length."""
+    def _proj_into(self, y, out, c3, ds, c1n):
+        """The block's projected residual when its c3 (input ``out``, chained into ``c1n`` or not) computes the
+        downsample conv ``ds`` of the block input ``y`` inside its own launch, else None."""
+        if ds is None or not {64: self.proj_l1, 128: self.proj_l2}.get(out.shape[3], False):
+            return None
+        proj = ops.ProjectedResidual(y, ds)
+        if ds[3] != 0 or y.shape[0] != out.shape[0] or proj.out_hw() != (out.shape[1], out.shape[2]) \
+                or tuple(ds[0].shape) != (c3[0].shape[0], 1, 1, y.shape[3]) \
+                or y.numel() * y.element_size() >= 1 << 31 or not (y.is_contiguous() and out.is_contiguous()):
+            return None
+        if not ops.conv1x1_proj_supported(out.shape[0] * out.shape[1] * out.shape[2], out.shape[3], c3[0].shape[0],
+                                          y.shape[3], ds[2], c1n[0].shape[0] if c1n is not None else 0, out.dtype,
+                                          self.policy):
+            return None
+        return proj
+
+    def _absorbed(self, y, f, relu=True):
+        """The bench hooks of a launch that another launch already stands for (a c1 the previous block's chained c3
+        computed, a downsample conv its block's c3 computes): its record in launch order, an empty event pair and one
+        launch-policy slot, so per-launch tables keep their length."""
         w, b, s, p = f
         if self.timing_args is not None:
-            self.timing_args.append((y, w, b, s, p, True, None, None))
+            self.timing_args.append((y, w, b, s, p, relu, None, None))
         if self.launch_policy is not None:
             self.launch_policy()
         if self.timing is not None:
@@ -430,8 +470,12 @@ class Encoder(nn.Module):
             out = self._frag_conv("c2frag", ops.conv3x3_frag, out, c2f)
         else:
             out = self._conv(out, c2, True)
-        idn = self._conv(y, ds, False) if ds is not None else y
         c1n = self._chain_into(out, c3, nxt)
+        idn = self._proj_into(y, out, c3, ds, c1n)
+        if idn is not None:   # the downsample launch's record keeps its place: after c2, before c3
+            self._absorbed(y, ds, False)
+        else:
+            idn = self._conv(y, ds, False) if ds is not None else y
         if c1n is not None:
             w, b, s, p = c3
             return self._launch((out, w, b, s, p, True, idn, None), ops.conv1x1_chain, out, c3, idn, c1n)

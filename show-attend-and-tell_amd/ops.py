@@ -175,11 +175,67 @@ def images_to_input(packed, layout=L.IMG_NCHW, dtype=torch.float32, c_pad=8, siz
     return out
 
 
+class ProjectedResidual:
+    """The residual of a stage's first bottleneck, not yet computed: the block input ``x`` [B,H,W,Kp] and the folded
+    downsample conv ``f`` = (w [N,1,1,Kp], bias f32, stride, pad 0) as the Encoder plan holds it.  conv2d_nhwc and
+    conv1x1_chain take it as ``residual=``: the c3 launch then forms the downsample output in registers
+    (sat_conv1x1_proj) where conv1x1_proj_supported, else the downsample conv is launched first -- the same bits."""
+
+    def __init__(self, x, f):
+        self.x, self.f = x, f
+
+    def out_hw(self):
+        s = self.f[2]
+        return (self.x.shape[1] - 1) // s + 1, (self.x.shape[2] - 1) // s + 1
+
+    def materialize(self, policy=None):
+        """The downsample conv as a launch of its own."""
+        return conv2d_nhwc(self.x, *self.f, False, policy=policy)
+
+
+def conv1x1_proj_supported(M, K, N, Kp, stride, N2, dtype, policy=None):
+    """True when the c3 (M pixels, K -> N channels) with a projected residual (Kp -> N channels at ``stride``), chained
+    into an N -> N2 c1 when N2 > 0, runs as ONE launch under ``policy``."""
+    return bool(L.lib().sat_conv1x1_proj_supported(M, K, N, Kp, stride, N2, L.dtype_code(dtype), L.policy_ptr(policy)))
+
+
+def _proj_launch(x, c3, proj, c1_next, policy):
+    """(y, x1 or None) from the projection kernel, or None where it does not apply (shape, dtype, policy, a block
+    input of 2 GiB or more, an unaligned or non-contiguous operand)."""
+    w, b = c3[0], c3[1]
+    wp, bp, stride, pad = proj.f
+    B, H, W, K = x.shape
+    N, Kp = w.shape[0], proj.x.shape[3]
+    w1, b1 = (c1_next[0], c1_next[1]) if c1_next is not None else (None, None)
+    N2 = w1.shape[0] if w1 is not None else 0
+    ts = [x, w, b, proj.x, wp, bp, w1, b1]
+    if pad != 0 or tuple(wp.shape) != (N, 1, 1, Kp) or tuple(w.shape[1:]) != (1, 1, K) or proj.out_hw() != (H, W) \
+            or proj.x.shape[0] != B or any(t.dtype != x.dtype for t in (w, proj.x, wp) + ((w1,) if N2 else ())) \
+            or any(t is not None and (not t.is_contiguous() or t.data_ptr() % 16) for t in ts) \
+            or proj.x.numel() * proj.x.element_size() >= 1 << 31 \
+            or not conv1x1_proj_supported(B * H * W, K, N, Kp, stride, N2, x.dtype, policy):
+        return None
+    L.require_device(*[t for t in ts if t is not None])
+    y = torch.empty(B, H, W, N, device=x.device, dtype=x.dtype)
+    x1 = torch.empty(B, H, W, N2, device=x.device, dtype=x.dtype) if N2 else None
+    L.check(L.lib().sat_conv1x1_proj(B, proj.x.shape[1], proj.x.shape[2], stride, K, N, Kp, N2, L.dtype_code(x.dtype),
+                                     L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(proj.x), L.ptr(wp), L.ptr(bp), L.ptr(y),
+                                     L.ptr(w1), L.ptr(b1), L.ptr(x1), L.policy_ptr(policy), L.stream_of(y)),
+            "sat_conv1x1_proj")
+    return y, x1
+
+
 def conv2d_nhwc(x, w, bias, stride, pad, relu, residual=None, out=None, out_hw=None, policy=None):
     """x [N,H,W,C] ; w [Cout,KH,KW,C] (same dtype) ; bias f32 [Cout].  ``pad`` pads top/left;
     ``out_hw`` (default: symmetric padding) fixes the output size; ``policy``: optional per-call kernel
-    selection (``sat_amd.Policy``)."""
+    selection (``sat_amd.Policy``).  ``residual`` may be a ProjectedResidual (a 1x1 / stride-1 conv + ReLU only)."""
     L.require_device(x, w)
+    if isinstance(residual, ProjectedResidual):
+        if relu and stride == 1 and pad == 0 and out is None and out_hw is None and w.shape[1] == w.shape[2] == 1:
+            r = _proj_launch(x, (w, bias), residual, None, policy)
+            if r is not None:
+                return r[0]
+        residual = residual.materialize(policy)
     N, H, W, C = x.shape
     Cout, KH, KW, Cw = w.shape
     assert Cw == C, (w.shape, x.shape)
@@ -196,6 +252,42 @@ def conv2d_nhwc(x, w, bias, stride, pad, relu, residual=None, out=None, out_hw=N
                                     L.ptr(residual), int(relu), L.ptr(y), L.policy_ptr(policy), L.stream_of(y)),
             "sat_conv2d_nhwc")
     return y
+
+
+def _stem_geom(x, w, stride, pad, out_hw):
+    N, H, W, C = x.shape
+    Cout, KH, KW, Cw = w.shape
+    assert Cw == C, (w.shape, x.shape)
+    if out_hw is None:
+        out_hw = ((H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1)
+    return L.SatConvGeom(N, H, W, C, KH, KW, stride, pad, out_hw[0], out_hw[1])
+
+
+def conv_stem_pool_supported(x, w, stride, pad, relu, pool, out_hw=None, policy=None):
+    """True when conv_stem_pool runs the conv (conv2d_nhwc's arguments) and the max pool ``pool`` = (k, stride, pad)
+    as ONE launch under ``policy``."""
+    g = _stem_geom(x, w, stride, pad, out_hw)
+    return bool(L.lib().sat_conv_stem_pool_supported(ctypes.byref(g), w.shape[0], L.dtype_code(x.dtype), int(relu),
+                                                     pool[0], pool[1], pool[2], L.policy_ptr(policy)))
+
+
+def conv_stem_pool(x, w, bias, stride, pad, relu, pool, out_hw=None, policy=None):
+    """maxpool2d_nhwc(conv2d_nhwc(x, w, bias, stride, pad, relu, out_hw=out_hw), *pool): ResNet152's stem.  One
+    launch that never writes the conv's output when conv_stem_pool_supported (and the operands are contiguous and
+    16-byte aligned), else the two launches; the same bits either way."""
+    L.require_device(x, w, bias)
+    ts = (x, w, bias)
+    if all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in ts) and w.dtype == x.dtype \
+            and conv_stem_pool_supported(x, w, stride, pad, relu, pool, out_hw, policy):
+        g = _stem_geom(x, w, stride, pad, out_hw)
+        k, ps, pp = pool
+        y = torch.empty(g.N, (g.OH + 2 * pp - k) // ps + 1, (g.OW + 2 * pp - k) // ps + 1, w.shape[0], device=x.device,
+                        dtype=x.dtype)
+        L.check(L.lib().sat_conv_stem_pool(ctypes.byref(g), w.shape[0], L.dtype_code(x.dtype), L.ptr(x), L.ptr(w),
+                                           L.ptr(bias), int(relu), k, ps, pp, L.ptr(y), L.policy_ptr(policy),
+                                           L.stream_of(y)), "sat_conv_stem_pool")
+        return y
+    return maxpool2d_nhwc(conv2d_nhwc(x, w, bias, stride, pad, relu, out_hw=out_hw, policy=policy), *pool)
 
 
 def mfma_frag_layout(w2d):
@@ -269,8 +361,14 @@ def conv1x1_chain(x, c3, residual, c1_next, policy=None):
     """A bottleneck's c3 and the next bottleneck's c1: y = relu(conv1x1(x, c3) + residual) and
     x1_next = relu(conv1x1(y, c1_next)), with c3 / c1_next = (w [Cout,1,1,Cin], bias f32, ...) as the Encoder plan
     folds them.  One launch when conv1x1_chain_supported (the c1 reads y's tile on chip), else the library issues
-    the two launches; either way both outputs are bit-identical to two conv2d_nhwc calls.  -> (y, x1_next)"""
+    the two launches; either way both outputs are bit-identical to two conv2d_nhwc calls.  ``residual`` may be a
+    ProjectedResidual.  -> (y, x1_next)"""
     L.require_device(x, c3[0], c1_next[0])
+    if isinstance(residual, ProjectedResidual):
+        r = _proj_launch(x, c3, residual, c1_next, policy) if x.is_contiguous() else None
+        if r is not None:
+            return r
+        residual = residual.materialize(policy)
     if not (x.is_contiguous() and residual.is_contiguous()):
         raise ValueError("conv1x1_chain: x and residual must be contiguous NHWC tensors")
     B, H, W, K = x.shape
