@@ -258,6 +258,85 @@ int sat_conv_stem_pool(const SatConvGeom* g, int Cout, int dtype, const void* x,
 int sat_maxpool2d_nhwc(int N, int H, int W, int C, int k, int stride, int pad, int dtype,
                        const void* x, void* y, int OH, int OW, void* stream);
 
+/* --- encoder backward (the trainable top of the trunk) ------------------- */
+/* Weight gradient of a 3x3 / stride-1 / pad-1 convolution (autograd's conv.weight gradient for the c2 of a
+ * torchvision Bottleneck, Bottleneck.forward through encoder.py:13-17, and for VGG19's block-5 convolutions,
+ * encoder.py:24-27):
+ *   dw[co][kh][kw][ci] (+)= sum over (n, oh, ow) of dz[n, oh, ow, co] * x[n, oh + kh - 1, ow + kw - 1, ci]
+ * x NHWC [N,H,W,Cin] and dz NHWC [N,H,W,Cout] in dtype, dw fp32 in the folded weight's [Cout][3][3][Cin] order;
+ * accumulate = 0 overwrites dw, 1 adds to it.  fp32 accumulation in a fixed order: the same call gives the same bits.
+ * One implicit-GEMM launch (M = Cout, N = 9 Cin, K = N H W, both operands k-major; csrc/convwgrad.hip) with a
+ * deterministic split-K over `workspace` (device, 16-byte aligned, at least
+ * sat_conv3x3_wgrad_workspace_bytes(...) bytes for the same shape and policy; the call zeroes its tickets itself).
+ * workspace = NULL runs unsplit.  policy->split_k > 0 forces that split count where K has that many 64-pixel
+ * k-tiles.  One workspace serves calls ordered on one stream.
+ * Shapes: Cin and Cout multiples of 128, any N, H, W >= 1, each tensor under 2 GiB.  Anything else fails with
+ * SAT_ERR_INVALID (_workspace_bytes: 0); there is no second path.
+ * dtype SAT_F32 (the parity path, not a performance path) gathers the im2col matrix [N H W][9 Cin] into the workspace
+ * (required; it must stay under 2 GiB) and runs the exact fp32 sat_gemm product on it. */
+size_t sat_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype, const SatPolicy* policy);
+int sat_conv3x3_wgrad(int N, int H, int W, int Cin, int Cout, int dtype, const void* x, const void* dz, float* dw,
+                      int accumulate, void* workspace, size_t workspace_bytes, const SatPolicy* policy,
+                      void* stream);
+
+/* out[i] = y[i] > 0 ? g[i] (+ add[i]) : 0 -- the gradient through a ReLU whose output y was kept (nn.ReLU backward:
+ * VGG19's conv + ReLU, encoder.py:24-27, and the three ReLUs of Bottleneck.forward); y NULL = no mask (a plain sum and
+ * cast: the identity shortcut's dX = dZ1 W1 + dZ3).  Each tensor in its own dtype (SAT_F32 | SAT_BF16), the sum in
+ * fp32, rounded once; 16-byte vectors when every pointer is 16-byte aligned.  out may alias g or add. */
+int sat_relu_mask(const void* y, int y_dtype, const void* g, int g_dtype, const void* add, int add_dtype, void* out,
+                  int out_dtype, int64_t n, void* stream);
+/* The forward fold of one convolution (+ eval-mode BatchNorm, train.py:122) as ONE launch, with the arithmetic of
+ * the encoder's plan in its operation order (torchvision conv + bn in eval mode, encoder.py:13-17,24-27):
+ *   scale = bn_weight / sqrt(bn_var + eps);  w' = weight * scale;  b' = bn_bias + (bias - bn_mean) * scale
+ * (bn_* NULL: w' = weight, b' = bias; bias NULL = 0).  weight: raw fp32 [Cout][Cin][KH][KW].  Writes
+ *   w_fold  [Cout][KH][KW][Cin] in dtype, b_fold fp32 [Cout], and (nullable) the input-gradient copy
+ *   w_igrad [Cin][KH-1-kh][KW-1-kw][Cout] in dtype: dX = conv(dZ, w_igrad) with the same stride 1 and padding. */
+int sat_conv_fold(int Cout, int Cin, int KH, int KW, int dtype, const float* weight, const float* bias,
+                  const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                  void* w_fold, float* b_fold, void* w_igrad, void* stream);
+/* One trainable convolution of the trunk's tail: its raw fp32 parameters (weight [Cout][Cin][KH][KW]; bias and the
+ * BatchNorm tensors nullable), its folded copies (sat_conv_fold) and where its gradients go (fp32, the parameters'
+ * shapes; the BN pair required with bn_weight, bias_grad with bias). */
+typedef struct {
+  const float* weight; const float* bias;
+  const float* bn_weight; const float* bn_mean; const float* bn_var; float eps;
+  const void* w_fold; const void* w_igrad;
+  float* weight_grad; float* bias_grad; float* bn_weight_grad; float* bn_bias_grad;
+} SatConvTrain;
+/* The fold's chain rule (autograd through eval-mode BatchNorm into the conv, encoder.py:13-17): from the folded
+ * gradients dw_fold fp32 [Cout][KH][KW][Cin] and db_fold fp32 [Cout], with s = bn_weight rstd, rstd = 1 / sqrt(var + eps):
+ *   weight_grad[co,ci,kh,kw] = dw_fold[co,kh,kw,ci] s[co]
+ *   bn_weight_grad[co] = rstd[co] (sum_k dw_fold[co,k] weight[co,k] + db_fold[co] (bias[co] - bn_mean[co]))
+ *   bn_bias_grad[co] = db_fold[co];  bias_grad[co] = db_fold[co] s[co]
+ * (no BatchNorm: s = 1, so the layout change and bias_grad = db_fold).  One workgroup per output channel, sums in a
+ * fixed order.  accumulate = 0 overwrites the gradients, 1 adds to them.  w_fold / w_igrad are not read. */
+int sat_conv_fold_backward(int Cout, int Cin, int KH, int KW, const float* dw_fold, const float* db_fold,
+                           const SatConvTrain* conv, int accumulate, void* stream);
+/* Backward of one identity-shortcut, stride-1 torchvision Bottleneck with eval-mode BatchNorm (Bottleneck.forward
+ * through encoder.py:13-17; ResNet152 layer4 blocks 1 and 2) in ONE call; C++ issues the launches:
+ *   dZ3 = [y > 0] dy;  dW3' = dZ3^T a2;  dA2 = dZ3 W3';  dZ2 = [a2 > 0] dA2;  dW2' = sat_conv3x3_wgrad(a1, dZ2);
+ *   dA1 = conv3x3(dZ2, c2->w_igrad);  dZ1 = [a1 > 0] dA1;  dW1' = dZ1^T x;  dx = dZ1 W1' + dZ3;
+ *   db' = column sums of dZ;  each (dW', db') through sat_conv_fold_backward into c1 / c2 / c3's gradients.
+ * x, y NHWC [N,H,W,Cin], a1 = relu(c1), a2 = relu(c2) NHWC [N,H,W,Cmid]: the forward's own tensors, in dtype; dy and
+ * dx (nullable) [N,H,W,Cin] in dtype.  Gradients handed between layers are rounded once to dtype; weight and bias
+ * gradients and every reduction stay fp32, in a fixed order.  Cin and Cmid multiples of 128.  workspace: device,
+ * 256-byte aligned, at least _workspace_bytes for the same arguments; one workspace serves calls ordered on one stream. */
+size_t sat_bottleneck_backward_workspace_bytes(int N, int H, int W, int Cin, int Cmid, int dtype,
+                                               const SatPolicy* policy);
+int sat_bottleneck_backward(int N, int H, int W, int Cin, int Cmid, int dtype, const void* x, const void* a1,
+                            const void* a2, const void* y, const SatConvTrain* c1, const SatConvTrain* c2,
+                            const SatConvTrain* c3, const void* dy, void* dx, int accumulate, void* workspace,
+                            size_t workspace_bytes, const SatPolicy* policy, void* stream);
+/* Backward of one 3x3 / stride-1 / pad-1 Conv2d + ReLU (VGG19's block-5 units, encoder.py:24-27) in ONE call:
+ *   dZ = [y > 0] dy;  dW' = sat_conv3x3_wgrad(x, dZ);  db' = column sums of dZ;  dx = conv3x3(dZ, c->w_igrad);
+ * x NHWC [N,H,W,Cin], y and dy [N,H,W,Cout], dx (nullable) [N,H,W,Cin], all in dtype.  Otherwise as
+ * sat_bottleneck_backward. */
+size_t sat_conv3x3_relu_backward_workspace_bytes(int N, int H, int W, int Cin, int Cout, int dtype,
+                                                 const SatPolicy* policy);
+int sat_conv3x3_relu_backward(int N, int H, int W, int Cin, int Cout, int dtype, const void* x, const void* y,
+                              const SatConvTrain* c, const void* dy, void* dx, int accumulate, void* workspace,
+                              size_t workspace_bytes, const SatPolicy* policy, void* stream);
+
 /* --- attention (attention.py:14-21), standalone module forward ----------- */
 /* Ws: workspace [B,L,E] fp32. Weights fp32 (U_w [E,E], W_w [E,D], v_w [E]); W_w_lp (bf16 copy)
  * required when dtype == SAT_BF16. context [B,D] fp32, alpha [B,L] fp32. */

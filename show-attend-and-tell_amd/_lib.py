@@ -64,6 +64,14 @@ class SatDecoderDims(ctypes.Structure):
                 ("seed_ptr", c_void_p), ("split_target", c_int), ("policy", ctypes.POINTER(SatPolicy))]
 
 
+class SatConvTrain(ctypes.Structure):
+    """One trainable convolution of the trunk's tail (include/sat_hip.h SatConvTrain)."""
+    _fields_ = [("weight", c_void_p), ("bias", c_void_p), ("bn_weight", c_void_p), ("bn_mean", c_void_p),
+                ("bn_var", c_void_p), ("eps", c_float), ("w_fold", c_void_p), ("w_igrad", c_void_p),
+                ("weight_grad", c_void_p), ("bias_grad", c_void_p), ("bn_weight_grad", c_void_p),
+                ("bn_bias_grad", c_void_p)]
+
+
 LAYOUT_FIELDS = ("embedding", "init_w", "init_b", "hcat_w", "hcat_b", "attW_w", "attW_b", "v_w", "v_b", "wih",
                  "bih", "fh_w", "fh_b", "fz_w", "fz_b", "fout_w", "fout_b", "do_w", "do_b", "total", "wih_ctx_t",
                  "hcat_t")
@@ -110,6 +118,26 @@ _SIGNATURES = [
                                    c_int, c_int, c_int, c_void_p, ctypes.POINTER(SatPolicy), c_void_p]),
     ("sat_maxpool2d_nhwc", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_int, c_int, c_void_p]),
+    ("sat_conv3x3_wgrad_workspace_bytes", c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                     ctypes.POINTER(SatPolicy)]),
+    ("sat_conv3x3_wgrad", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_size_t, ctypes.POINTER(SatPolicy), c_void_p]),
+    ("sat_relu_mask", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]),
+    ("sat_conv_fold", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("sat_conv_fold_backward", c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(SatConvTrain),
+                                       c_int, c_void_p]),
+    ("sat_bottleneck_backward_workspace_bytes", c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                           ctypes.POINTER(SatPolicy)]),
+    ("sat_bottleneck_backward", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, ctypes.POINTER(SatConvTrain), ctypes.POINTER(SatConvTrain),
+                                        ctypes.POINTER(SatConvTrain), c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                        ctypes.POINTER(SatPolicy), c_void_p]),
+    ("sat_conv3x3_relu_backward_workspace_bytes", c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                             ctypes.POINTER(SatPolicy)]),
+    ("sat_conv3x3_relu_backward", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          ctypes.POINTER(SatConvTrain), c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                          ctypes.POINTER(SatPolicy), c_void_p]),
     ("sat_attention_forward", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),

@@ -81,3 +81,16 @@ def allreduce_grads(decoder, group=None):
         dist.all_reduce(bucket, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=group)
         if not avg:
             bucket.div_(world)
+
+
+def all_reduce_tail_grads(encoder, group=None):
+    """Mean all-reduce of a fine-tuned encoder's tail gradients: ONE collective over ``Encoder.tail_grad_flat`` (the
+    views every tail parameter's .grad points into), after the decoder's buckets.  Without it the ranks' trunks would
+    drift apart silently.  A no-op before the first backward (no gradient buffer yet)."""
+    flat = encoder.tail_grad_flat
+    if flat is None:
+        return
+    avg = dist.get_backend(group) == "nccl"
+    dist.all_reduce(flat, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=group)
+    if not avg:
+        flat.div_(dist.get_world_size(group))

@@ -25,14 +25,22 @@ activations:
   * the final NHWC tensor already IS ``permute(0,2,3,1).view(B,-1,C)``
     (encoder.py:37-39): no transpose.
 
-The trunk is frozen (``requires_grad=False``) and forward-only for every
-network: the reference freezes only VGG19 (encoder.py:29-31) and lets ResNet152
-accumulate encoder gradients the optimiser never reads (train.py:71); skipping
-that dead backward leaves every trained value identical.
+By default the trunk is frozen (``requires_grad=False``) and forward-only for
+every network: the reference freezes only VGG19 (encoder.py:29-31) and lets
+ResNet152 accumulate encoder gradients the optimiser never reads (train.py:71);
+skipping that dead backward leaves every trained value identical.
+``Encoder(..., fine_tune=n)`` / ``Encoder.fine_tune(n)`` makes the last ``n``
+units trainable (ResNet152: layer4's identity bottlenecks, n <= 2; VGG19: the
+block-5 convolutions, n <= 4): with grad enabled the forward runs plan steps
+``tail_start()`` .. end through ``_TailFn``, whose backward consumes the decoder's
+``dL/d(img_features)`` and leaves the tail's gradients in views of
+``Encoder.tail_grad_flat``.  BatchNorm stays in eval mode.
 Pretrained ImageNet weights are a download in the reference; here weights are
 randomly initialised with torchvision's scheme unless a state_dict is loaded.
 DenseNet161 (argparse choice, no BASELINE config) is out of scope.
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 
@@ -129,8 +137,123 @@ def _init_like_torchvision(module):
             nn.init.constant_(m.bn3.weight, 0.2)
 
 
+FINE_TUNE_LIMIT = {"resnet152": 2, "vgg19": 4}
+VGG19_TAIL_CONVS = (28, 30, 32, 34)   # block 5: net.<i>, in forward order
+
+
+class _TailFn(torch.autograd.Function):
+    """The trainable tail of the trunk (plan steps k .. end) with a backward: the forward is the plan's own c1 / c2 /
+    c3 (or conv) launches, keeping each unit's activations; the backward is one C-ABI call per unit
+    (sat_bottleneck_backward / sat_conv3x3_relu_backward), last unit first, into views of ``Encoder.tail_grad_flat``."""
+
+    @staticmethod
+    def forward(ctx, act, enc, first, *params):
+        plan = enc._plan
+        k = enc.tail_start()
+        y, saved = act, []
+        for step in plan[k + first:]:
+            y, sv = enc._tail_unit_forward(y, step)
+            saved.append(sv)
+        ctx.enc, ctx.first, ctx.saved = enc, first, saved
+        ctx.trains = [enc._tail_state[first + i] for i in range(len(saved))]
+        B, H, W, C = y.shape
+        return y.view(B, H * W, C)
+
+    @staticmethod
+    def backward(ctx, d_feats):
+        enc, saved = ctx.enc, ctx.saved
+        out = saved[-1][-1]
+        if d_feats.dtype != out.dtype:
+            raise TypeError("sat_amd.Encoder.backward: grad dtype must match the features")
+        dy = d_feats.contiguous().view(out.shape)
+        accumulate = enc._attach_tail_grads()
+        lib = L.lib()
+        dt = L.dtype_code(out.dtype)
+        pol = L.policy_ptr(enc.policy)
+        sizes = []
+        for sv in saved:
+            N, H, W, Cin = sv[0].shape
+            fn = lib.sat_bottleneck_backward_workspace_bytes if len(sv) == 4 else \
+                lib.sat_conv3x3_relu_backward_workspace_bytes
+            sizes.append(fn(N, H, W, Cin, sv[1].shape[3], dt, pol))
+            if sizes[-1] == 0:
+                raise RuntimeError(f"sat_amd.Encoder.backward: unsupported tail shape {tuple(sv[0].shape)}")
+        ws = torch.empty(max(sizes), device=out.device, dtype=torch.uint8)
+        stream = L.stream_of(out)
+        for i in reversed(range(len(saved))):
+            sv, tr = saved[i], ctx.trains[i]
+            x = sv[0]
+            N, H, W, Cin = x.shape
+            dx = torch.empty_like(x) if i > 0 or ctx.needs_input_grad[0] else None
+            cts = [t.conv_train(enc.tail_grad_flat) for t in tr]
+            if len(sv) == 4:
+                L.check(lib.sat_bottleneck_backward(N, H, W, Cin, sv[1].shape[3], dt, L.ptr(x), L.ptr(sv[1]),
+                                                    L.ptr(sv[2]), L.ptr(sv[3]), ctypes.byref(cts[0]),
+                                                    ctypes.byref(cts[1]), ctypes.byref(cts[2]), L.ptr(dy), L.ptr(dx),
+                                                    int(accumulate), L.ptr(ws), ws.numel(), pol, stream),
+                        "sat_bottleneck_backward")
+            else:
+                L.check(lib.sat_conv3x3_relu_backward(N, H, W, Cin, sv[1].shape[3], dt, L.ptr(x), L.ptr(sv[1]),
+                                                      ctypes.byref(cts[0]), L.ptr(dy), L.ptr(dx), int(accumulate),
+                                                      L.ptr(ws), ws.numel(), pol, stream),
+                        "sat_conv3x3_relu_backward")
+            dy = dx
+        ctx.saved = None
+        return (dy if ctx.needs_input_grad[0] else None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+class _TailConv:
+    """One trainable conv of the tail: its modules, its folded buffers (written in place by sat_conv_fold at every
+    refresh) and the offsets of its gradients in ``Encoder.tail_grad_flat``."""
+
+    def __init__(self, conv, bn, device, dtype, frag):
+        self.conv, self.bn = conv, bn
+        co, ci, kh, kw = conv.weight.shape
+        self.w_fold = torch.empty(co, kh, kw, ci, device=device, dtype=dtype)
+        self.b_fold = torch.empty(co, device=device, dtype=torch.float32)
+        self.w_igrad = torch.empty(ci, kh, kw, co, device=device, dtype=dtype) if kh == 3 else None
+        self.frag = torch.empty(co, kh * kw * ci, device=device, dtype=dtype) if frag else None
+        self.offsets = {}   # parameter -> element offset in tail_grad_flat
+
+    def params(self):
+        ps = [self.conv.weight] + ([self.conv.bias] if self.conv.bias is not None else [])
+        return ps + ([self.bn.weight, self.bn.bias] if self.bn is not None else [])
+
+    def fold(self, stream):
+        c, bn = self.conv, self.bn
+        co, ci, kh, kw = c.weight.shape
+        lib = L.lib()
+        L.check(lib.sat_conv_fold(co, ci, kh, kw, L.dtype_code(self.w_fold.dtype), L.ptr(c.weight), L.ptr(c.bias),
+                                  L.ptr(bn.weight if bn else None), L.ptr(bn.bias if bn else None),
+                                  L.ptr(bn.running_mean if bn else None), L.ptr(bn.running_var if bn else None),
+                                  bn.eps if bn else 0.0, L.ptr(self.w_fold), L.ptr(self.b_fold), L.ptr(self.w_igrad),
+                                  stream), "sat_conv_fold")
+        if self.frag is not None:   # the forward reads this conv's weight in the fragment layout
+            L.check(lib.sat_mfma_frag_layout(co, kh * kw * ci, L.ptr(self.w_fold), L.ptr(self.frag), stream),
+                    "sat_mfma_frag_layout")
+
+    def folded(self):
+        return (self.w_fold, self.b_fold, self.conv.stride[0], self.conv.padding[0])
+
+    def conv_train(self, flat):
+        c, bn = self.conv, self.bn
+        base = flat.data_ptr()
+
+        def g(p):
+            return None if p is None else ctypes.c_void_p(base + 4 * self.offsets[p])
+        t = L.SatConvTrain()
+        t.weight, t.bias = c.weight.data_ptr(), L.ptr(c.bias)
+        if bn is not None:
+            t.bn_weight, t.bn_mean, t.bn_var, t.eps = (bn.weight.data_ptr(), bn.running_mean.data_ptr(),
+                                                       bn.running_var.data_ptr(), bn.eps)
+            t.bn_weight_grad, t.bn_bias_grad = g(bn.weight), g(bn.bias)
+        t.w_fold, t.w_igrad = self.w_fold.data_ptr(), L.ptr(self.w_igrad)
+        t.weight_grad, t.bias_grad = g(c.weight), g(c.bias)
+        return t
+
+
 class Encoder(nn.Module):
-    def __init__(self, network="vgg19", dtype=torch.float32):
+    def __init__(self, network="vgg19", dtype=torch.float32, fine_tune=0):
         super().__init__()
         self.network = network
         if network == "resnet152":
@@ -190,6 +313,139 @@ class Encoder(nn.Module):
         # per-call kernel selection for the conv launches (sat_amd.Policy / SatPolicy; None = the library's
         # defaults): A/B measurements and tests only
         self.policy = None
+        # the trainable tail (fine_tune): units, their folded buffers per (device, dtype), the flat gradient buffer
+        self._fine_tune = 0
+        self._tail_state = None
+        self._tail_state_key = None
+        self._tail_key_done = None
+        self.tail_grad_flat = None
+        if fine_tune:
+            self.fine_tune(fine_tune)
+
+    # ---- the trainable tail ---------------------------------------------------
+    def _tail_units(self, n=None):
+        """The last ``n`` trainable units in forward order, each a list of (conv, bn or None)."""
+        n = self._fine_tune if n is None else n
+        if n == 0:
+            return []
+        if self.network == "resnet152":   # the identity bottlenecks of layer4, counted from the end
+            blocks = list(self.net[7])[-n:]
+            return [[(b.conv1, b.bn1), (b.conv2, b.bn2), (b.conv3, b.bn3)] for b in blocks]
+        return [[(self.net[i], None)] for i in VGG19_TAIL_CONVS[-n:]]
+
+    def fine_tune(self, n):
+        """Make the last ``n`` units of the trunk trainable (0 = the frozen encoder): ResNet152's layer4 identity
+        bottlenecks from the end (net.7.2, net.7.1), VGG19's block-5 convolutions (net.34, .32, .30, .28).  Their conv
+        weights (and biases) and BatchNorm affine parameters get ``requires_grad``; BatchNorm stays in eval mode and
+        its running statistics are never touched."""
+        limit = FINE_TUNE_LIMIT[self.network]
+        if not 0 <= int(n) <= limit:
+            raise ValueError(f"Encoder.fine_tune: {self.network} has at most {limit} trainable units, got {n}")
+        self._fine_tune = int(n)
+        for p in self.net.parameters():
+            p.requires_grad = False
+        for unit in self._tail_units():
+            for conv, bn in unit:
+                for p in [conv.weight, conv.bias] + ([bn.weight, bn.bias] if bn is not None else []):
+                    if p is not None:
+                        p.requires_grad = True
+        self._plan = self._plan_key = self._tail_state = self._tail_state_key = self._tail_key_done = None
+        self.tail_grad_flat = None
+        return self
+
+    def tail_parameters(self):
+        """The trainable tail's parameters in ``tail_grad_flat`` order."""
+        return [p for unit in self._tail_units() for conv, bn in unit
+                for p in [conv.weight, conv.bias] + ([bn.weight, bn.bias] if bn is not None else []) if p is not None]
+
+    def _plan_len(self):
+        return 52 if self.network == "resnet152" else 20   # stem, pool, 50 blocks | 16 convs, 4 pools
+
+    def tail_start(self):
+        """The plan index where the trainable tail begins (the plan's length when nothing is trainable)."""
+        return self._plan_len() - self._fine_tune
+
+    def _tail_tensors(self):
+        """Parameters and buffers of the tail's units: their versions make the tail part of the state key."""
+        ts = []
+        for unit in self._tail_units():
+            for conv, bn in unit:
+                ts += list(conv.parameters()) + (list(bn.parameters()) + list(bn.buffers()) if bn is not None else [])
+        return ts
+
+    def _tail_key(self):
+        return tuple(t._version for t in self._tail_tensors())
+
+    def _refold_tail(self, device, dtype):
+        """Fold the tail's convs with sat_conv_fold into their own buffers and point the tail's plan entries at them;
+        the prefix's entries are not touched."""
+        skey = (device, dtype)
+        if self._tail_state is None or self._tail_state_key != skey:
+            state = []
+            for unit in self._tail_units():
+                convs = []
+                for conv, bn in unit:
+                    if conv.weight.dtype != torch.float32 or not conv.weight.is_contiguous():
+                        raise TypeError("Encoder.fine_tune: the tail's parameters must be contiguous float32")
+                    cmid = conv.out_channels
+                    hw = 7 if self.network == "resnet152" else 14
+                    frag = conv.kernel_size == (3, 3) and conv.in_channels == cmid and dtype == torch.bfloat16 \
+                        and ops.conv3x3_frag_supported(hw, hw, cmid, dtype)
+                    convs.append(_TailConv(conv, bn, device, dtype, frag))
+                state.append(convs)
+            self._tail_state, self._tail_state_key = state, skey
+            self.tail_grad_flat = None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        k = self.tail_start()
+        for i, convs in enumerate(self._tail_state):
+            for tc in convs:
+                tc.fold(stream)
+            if len(convs) == 3:
+                c1, c2, c3 = convs
+                self._plan[k + i] = ("block", c1.folded(), c2.folded(), c3.folded(), None, None,
+                                     (c2.frag, c2.b_fold) if c2.frag is not None else None)
+            else:
+                tc = convs[0]
+                self._plan[k + i] = ("conv", tc.folded(), True, (tc.frag, tc.b_fold) if tc.frag is not None else None)
+
+    def _attach_tail_grads(self):
+        """Make the tail parameters' .grad views of ``tail_grad_flat`` (the decoder's rule, Decoder._attach_grads);
+        return True if they already were: the backward then accumulates, else it overwrites."""
+        params = self.tail_parameters()
+        if self.tail_grad_flat is None or self.tail_grad_flat.device != params[0].device:
+            total, off = 0, {}
+            for p in params:
+                off[p] = total
+                total += (p.numel() + 63) // 64 * 64   # 256-byte aligned views
+            self.tail_grad_flat = torch.zeros(total, device=params[0].device, dtype=torch.float32)
+            for convs in self._tail_state:
+                for tc in convs:
+                    tc.offsets = {p: off[p] for p in tc.params()}
+        attached = True
+        base = self.tail_grad_flat
+        for convs in self._tail_state:
+            for tc in convs:
+                for p, o in tc.offsets.items():
+                    if p.grad is None or p.grad.data_ptr() != base.data_ptr() + 4 * o:
+                        attached = False
+                        p.grad = base[o:o + p.numel()].view(p.shape)
+        return attached
+
+    def _tail_unit_forward(self, y, step):
+        """One unit of the tail as the plan runs it (separate c1 / c2 / c3 launches, layer4's form) -> (its output,
+        the activations its backward needs: the forward's own tensors)."""
+        if step[0] == "conv":
+            out = self._run_step(y, step)[0]
+            return out, (y, out)
+        _, c1, c2, c3, ds, fused, c2f = step
+        a1 = self._conv(y, c1, True)
+        if c2f is not None and self.c2_frag and a1.shape[1] in self.c2_frag_sizes \
+                and ops.conv3x3_frag_supported(a1.shape[1], a1.shape[2], a1.shape[3], a1.dtype):
+            a2 = self._frag_conv("c2frag", ops.conv3x3_frag, a1, c2f)
+        else:
+            a2 = self._conv(a1, c2, True)
+        out = self._conv(a2, c3, True, residual=y)
+        return out, (y, a1, a2, out)
 
     def _launch(self, record, fn, *args, **kw):
         """One conv launch with the bench's hooks: its arguments recorded, an event pair around it,
@@ -244,8 +500,11 @@ class Encoder(nn.Module):
         return (w.contiguous().to(self.compute_dtype), b.contiguous(), conv.stride[0], conv.padding[0])
 
     def _state_key(self, device, dtype):
-        return (device, dtype, tuple(p._version for p in self.net.parameters()),
-                tuple(b._version for b in self.net.buffers()))
+        """The prefix part of the state key: every parameter and buffer outside the trainable tail (all of them when
+        nothing is trainable).  The tail's part is _tail_key()."""
+        tail = {id(t) for t in self._tail_tensors()}
+        return (device, dtype, tuple(p._version for p in self.net.parameters() if id(p) not in tail),
+                tuple(b._version for b in self.net.buffers() if id(b) not in tail))
 
     def _build_plan(self, device, dtype):
         self.compute_dtype = dtype
@@ -315,11 +574,22 @@ class Encoder(nn.Module):
         w, b, _, _ = self._fold(blk.conv2, blk.bn2)
         return ops.mfma_frag_layout(w.reshape(w.shape[0], -1)), b
 
-    def compiled_plan(self, device, dtype):
+    def compiled_plan(self, device, dtype, tail=True):
+        """The plan for (device, dtype).  ``tail=False`` leaves a fine-tuned encoder's tail entries as they are: a
+        forward that stops before tail_start() (the frozen prefix running ahead on a side stream) must not re-fold
+        weights the optimiser may still be writing on another stream."""
         key = self._state_key(device, dtype)
         if self._plan is None or self._plan_key != key:
             self._build_plan(device, dtype)
             self._plan_key = key
+            self._tail_key_done = None
+        if tail and self._fine_tune and torch.device(device).type == "cuda":
+            # a weight update of the tail re-folds the tail's entries only (HIP launches), always by sat_conv_fold:
+            # train and eval forwards of a fine-tuned encoder read identical weights
+            tkey = (self._tail_key(), device, dtype)
+            if self._tail_key_done != tkey:
+                self._refold_tail(device, dtype)
+                self._tail_key_done = tkey
         return self._plan
 
     def stage_starts(self, device=None, dtype=None):
@@ -341,8 +611,25 @@ class Encoder(nn.Module):
         packed = isinstance(x, PackedImages)
         L.require_device(x.pixels if packed else x)
         dtype = dtype or self.compute_dtype
-        plan = self.compiled_plan((x.pixels if packed else x).device, dtype)
+        dev = (x.pixels if packed else x).device
+        plan = self.compiled_plan(dev, dtype, tail=False)
         start, stop = steps if steps is not None else (0, len(plan))
+        k = self.tail_start()
+        if stop > k:   # the slice reads the tail's entries: re-fold them (on this stream) if their weights changed
+            plan = self.compiled_plan(dev, dtype)
+        if self._fine_tune and torch.is_grad_enabled() and stop == len(plan) and start < stop:
+            # the frozen prefix as always, under no_grad; the tail through an autograd Function that keeps the
+            # activations its backward needs
+            first = max(start, k) - k
+            if start < k:
+                with torch.no_grad():
+                    x = self._forward_plain(x, packed, dtype, plan, start, k)
+            elif not x.is_contiguous():
+                raise ValueError("Encoder: the tail's input must be a contiguous NHWC activation")
+            return _TailFn.apply(x, self, first, *self.tail_parameters())
+        return self._forward_plain(x, packed, dtype, plan, start, stop)
+
+    def _forward_plain(self, x, packed, dtype, plan, start, stop):
         if packed:   # decoded uint8 images: resize + normalize straight into the first layer's layout
             if start > 0:
                 raise ValueError("Encoder: packed images enter at plan step 0")

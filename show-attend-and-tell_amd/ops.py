@@ -385,6 +385,41 @@ def conv1x1_chain(x, c3, residual, c1_next, policy=None):
     return y, x1
 
 
+def conv3x3_wgrad_workspace_bytes(x_shape, cout, dtype, policy=None):
+    """Bytes of the split-K workspace conv3x3_wgrad uses for an NHWC input of ``x_shape`` and ``cout`` output channels
+    under ``policy``; 0 for a shape the kernel refuses."""
+    N, H, W, C = x_shape
+    return int(L.lib().sat_conv3x3_wgrad_workspace_bytes(N, H, W, C, cout, L.dtype_code(dtype), L.policy_ptr(policy)))
+
+
+def conv3x3_wgrad(x, dz, out=None, accumulate=False, policy=None, workspace=True):
+    """Weight gradient of a 3x3 / stride-1 / pad-1 conv: x NHWC [N,H,W,Cin], dz NHWC [N,H,W,Cout] (bf16) ->
+    dw fp32 [Cout,3,3,Cin] (the folded weight's order), ``out`` overwritten or, with ``accumulate``, added to.
+    Cin and Cout multiples of 128; anything else raises (no second path).  ``workspace``: True = a split-K workspace
+    allocated for this call, a uint8 device tensor of at least conv3x3_wgrad_workspace_bytes, or None (unsplit)."""
+    L.require_device(x, dz, out)
+    if x.dtype != dz.dtype or x.shape[:3] != dz.shape[:3]:
+        raise ValueError(f"conv3x3_wgrad: x{tuple(x.shape)} {x.dtype} and dz{tuple(dz.shape)} {dz.dtype} do not match")
+    if not (x.is_contiguous() and dz.is_contiguous()):
+        raise ValueError("conv3x3_wgrad: x and dz must be contiguous NHWC tensors")
+    N, H, W, Cin = x.shape
+    Cout = dz.shape[3]
+    if out is None:
+        if accumulate:
+            raise ValueError("conv3x3_wgrad: accumulate needs the buffer to add to")
+        out = torch.empty(Cout, 3, 3, Cin, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (Cout, 3, 3, Cin) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("conv3x3_wgrad: out must be a contiguous fp32 [Cout,3,3,Cin] tensor")
+    if workspace is True:
+        workspace = torch.empty(conv3x3_wgrad_workspace_bytes(x.shape, Cout, x.dtype, policy), dtype=torch.uint8,
+                                device=x.device)
+    ws_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    L.check(L.lib().sat_conv3x3_wgrad(N, H, W, Cin, Cout, L.dtype_code(x.dtype), L.ptr(x), L.ptr(dz), L.ptr(out),
+                                      int(accumulate), L.ptr(workspace) if ws_bytes else None, ws_bytes,
+                                      L.policy_ptr(policy), L.stream_of(out)), "sat_conv3x3_wgrad")
+    return out
+
+
 def maxpool2d_nhwc(x, k, stride, pad=0):
     L.require_device(x)
     N, H, W, C = x.shape

@@ -106,6 +106,9 @@ class Adam(torch.optim.Optimizer):
                     mv, vv = m[off:off + n], v[off:off + n]
                 else:
                     pv, gv, mv, vv = p.view(-1), p.grad.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1)
+                    # the kernel writes through the pointer: tell whoever keys on the parameter's version (the
+                    # encoder's plan refresh of a fine-tuned tail) that it changed
+                    torch.autograd.graph.increment_version(p)
                 ops.adam_step_(pv, gv, mv, vv, lp, b1, b2, eps, lr / bc1, math.sqrt(bc2))
             refreshed = set()
             for p, owner, st in items:

@@ -22,6 +22,10 @@ so it cannot be disabled, as in train.py:450), plus:
   --beam-eval K   also caption every validation / test batch with batched beam search of width K
                   (Decoder.caption_batch) and log {mode}_beam_bleu1..4 for the generated sentences
                   (default 0 = off: only the reference's teacher-forced argmax BLEU)
+  --fine-tune-encoder N  train the last N units of the trunk (resnet152: layer4's identity bottlenecks, N <= 2; vgg19:
+                  the block-5 convolutions, N <= 4) with --encoder-lr (default 1e-5) as a second Adam param group;
+                  the frozen prefix of batch i+1 still runs ahead on the side stream, the tail runs inside the step;
+                  each epoch also saves encoder_<network>_<epoch>.pth, which model_config.json then names
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -157,6 +161,10 @@ def parse(argv=None):
                    help="beam width of an extra generated-caption BLEU in evaluation (0 = off)")
     p.add_argument("--bert-embeddings", type=str, default=None,
                    help="local bert-base-uncased word-embedding table [30522, 768] (weights_only)")
+    p.add_argument("--fine-tune-encoder", type=int, default=0,
+                   help="train the last N units of the trunk (resnet152: layer4's identity bottlenecks, N <= 2; "
+                        "vgg19: the block-5 convolutions, N <= 4); 0 = frozen encoder")
+    p.add_argument("--encoder-lr", type=float, default=1e-5, help="Adam learning rate of the trainable encoder units")
     return p.parse_args(argv)
 
 
@@ -189,7 +197,7 @@ def build(args, device):
     else:
         word_dict = json.load(open(os.path.join(args.data, "word_dict.json")))
         vocab = len(word_dict)
-    encoder = sat_amd.Encoder(args.network, dtype=dt)
+    encoder = sat_amd.Encoder(args.network, dtype=dt, fine_tune=args.fine_tune_encoder)
     if args.encoder_weights:
         encoder.load_state_dict(torch.load(args.encoder_weights, map_location="cpu", weights_only=True))
     bert_w = None
@@ -254,15 +262,24 @@ def encoded_batches(loader, encoder, device, dt, max_steps, overlap):
     reference never optimises ResNet152's)."""
     main = torch.cuda.current_stream(device)
     side = torch.cuda.Stream(device) if overlap else main
+    # a fine-tuned encoder: only the frozen prefix (plan steps 0 .. tail_start(), which read no trainable weight) runs
+    # ahead; the tail runs on the main stream inside the step, after the previous step's update
+    k = encoder.tail_start() if getattr(encoder, "_fine_tune", 0) else None
 
     def encode(imgs, captions):
         with torch.cuda.stream(side), torch.no_grad():
             imgs = imgs.to(device, non_blocking=True)   # a Tensor, or PackedImages (uint8, native size)
             captions = captions.to(device, non_blocking=True)
-            feats = encoder(imgs, dtype=dt)
+            feats = encoder(imgs, dtype=dt) if k is None else encoder(imgs, dtype=dt, steps=(0, k))
             ev = torch.cuda.Event()
             ev.record(side)
         return feats, captions, ev
+
+    def tail(batch):
+        if k is None:
+            return batch
+        batch_idx, act, caps = batch
+        return batch_idx, encoder(act, dtype=dt, steps=(k, encoder._plan_len())), caps
 
     pending = None
     for batch_idx, (imgs, captions, _) in enumerate(loader):
@@ -270,7 +287,7 @@ def encoded_batches(loader, encoder, device, dt, max_steps, overlap):
             break
         nxt = encode(imgs, captions)
         if pending is not None:
-            yield pending
+            yield tail(pending)
         feats, caps, ev = nxt
         main.wait_event(ev)
         if side is not main:   # produced on the side stream, consumed on the main one
@@ -278,7 +295,7 @@ def encoded_batches(loader, encoder, device, dt, max_steps, overlap):
             caps.record_stream(main)
         pending = (batch_idx, feats, caps)
     if pending is not None:
-        yield pending
+        yield tail(pending)
 
 
 def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, log, grad_ar=None):
@@ -297,6 +314,8 @@ def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, l
         loss.backward()   # with DP the head bucket's all-reduce starts inside it, beside BPTT
         if grad_ar is not None:
             grad_ar.wait()
+            if args.fine_tune_encoder:   # the tail's gradients, after the decoder's buckets: ranks must not drift
+                sat_dist.all_reduce_tail_grads(encoder)
         opt.step()
         meters.update(loss, metrics)
         if batch_idx % args.log_interval == 0:   # train.py:183-192
@@ -383,7 +402,11 @@ def main(argv=None):
         # no layer3 block fused: the unfused c2 / c3 half-image kernels leave CUs to the decoder
         # (profiles/r2_s62_sched.txt)
         encoder.fuse_blocks = False
-    opt = sat_amd.Adam(decoder.parameters(), lr=args.lr)
+    if args.fine_tune_encoder:   # the tail's parameters as a second param group (one launch per tensor)
+        opt = sat_amd.Adam([{"params": list(decoder.parameters())},
+                            {"params": encoder.tail_parameters(), "lr": args.encoder_lr}], lr=args.lr)
+    else:
+        opt = sat_amd.Adam(decoder.parameters(), lr=args.lr)
     grad_ar = sat_dist.GradAllReduce(decoder) if world > 1 else None
     sched = torch.optim.lr_scheduler.StepLR(opt, args.step_size)
     train_loader = loaders(args, "train", rank, world)
@@ -403,6 +426,10 @@ def main(argv=None):
             torch.save(decoder.state_dict(), os.path.join(args.out, f"model_{args.network}_{epoch}.pth"))
             cfg = dict(vars(args))
             cfg["encoder_weights"] = os.path.abspath(enc_path)
+            if args.fine_tune_encoder:   # the tuned trunk of this epoch, beside the decoder's checkpoint
+                tuned = os.path.join(args.out, f"encoder_{args.network}_{epoch}.pth")
+                torch.save({k: v.detach().cpu() for k, v in encoder.state_dict().items()}, tuned)
+                cfg["encoder_weights"] = os.path.abspath(tuned)
             if args.synthetic and word_dict:   # generate_caption.py reads <data>/word_dict.json
                 cfg["data"] = args.out
                 with open(os.path.join(args.out, "word_dict.json"), "w") as f:
