@@ -499,6 +499,22 @@ int sat_images_to_input(const uint8_t* pixels, const int64_t* offsets, const int
                         int max_w, int OH, int OW, const float* mean, const float* std, int layout, int c_pad,
                         int dtype, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* --- row gather / scatter against a device-resident table (the feature cache: the frozen trunk's output per image,
+ * computed once and kept in HBM instead of re-encoding dataset.py's repeated image per caption) ----
+ *   sat_rows_gather :  out[i, :]        = table[idx[i], :]   for i < n
+ *   sat_rows_scatter:  table[idx[i], :] = src[i, :]          for i < n  (idx distinct: rows of equal index race)
+ * table is [n_rows, row_elems], out / src [n, row_elems], all contiguous, dtype SAT_BF16 or SAT_F32; idx is a DEVICE
+ * array read by the kernel, so a captured launch follows a rewritten index buffer.  An index outside [0, n_rows)
+ * makes the gather write a zero row and the scatter skip the row; each such row adds 1 to *n_bad (device, nullable,
+ * zeroed by the caller).  Nothing but out, or the addressed table rows, is written.  Rows move as 16-B vectors when
+ * the row bytes and both base pointers are 16-B aligned, else element by element; every address is 64-bit (a table
+ * may exceed 2^32 bytes).  Null table / src / idx / out, n < 0, n_rows <= 0, row_elems <= 0 or another dtype:
+ * SAT_ERR_INVALID before any launch; n == 0 is a successful no-op. */
+int sat_rows_gather(const void* table, int64_t n_rows, int64_t row_elems, int dtype, const int64_t* idx, int n,
+                    void* out, int32_t* n_bad, void* stream);
+int sat_rows_scatter(const void* src, int n, int64_t row_elems, int dtype, const int64_t* idx, void* table,
+                     int64_t n_rows, int32_t* n_bad, void* stream);
+
 /* --- optimiser (torch.optim.Adam single-tensor step, train.py:71,164) ---- */
 int sat_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                   void* param_lp, int64_t n, float beta1, float beta2, float eps,

@@ -11,8 +11,9 @@ from .attention import Attention
 from .data import PackedImages, collate_packed
 from .decoder import Decoder
 from .encoder import Encoder
+from .feature_cache import FeatureCache
 from .loss import caption_loss, special_ids, StepMetrics, RunningMeters
 from .optim import Adam
 
 __all__ = ["Attention", "Decoder", "Encoder", "caption_loss", "special_ids", "StepMetrics", "RunningMeters", "Adam",
-           "PackedImages", "collate_packed"]
+           "PackedImages", "collate_packed", "FeatureCache"]

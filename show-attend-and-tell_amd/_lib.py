@@ -188,6 +188,8 @@ _SIGNATURES = [
     ("sat_images_to_input", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                     ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_int, c_int, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    ("sat_rows_gather", c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("sat_rows_scatter", c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     ("sat_adam_step", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
                               c_float, c_float, c_float, c_void_p]),
 ]

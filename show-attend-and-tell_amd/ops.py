@@ -431,6 +431,52 @@ def maxpool2d_nhwc(x, k, stride, pad=0):
     return y
 
 
+def _rows_args(what, table, idx, batch, n_bad):
+    """Checks shared by rows_gather / rows_scatter: ``table`` [n_rows, ...] and ``batch`` [n, ...] contiguous with equal
+    row shapes and dtype, ``idx`` int64 [n], ``n_bad`` one int32 -> (n_rows, row_elems)."""
+    L.require_device(table, idx, batch, n_bad)
+    if table.dim() < 1 or table.shape[0] == 0 or not table.is_contiguous():
+        raise ValueError(f"{what}: table must be a contiguous [n_rows, ...] tensor with n_rows > 0")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError(f"{what}: idx must be a contiguous int64 vector")
+    if batch.dtype != table.dtype or tuple(batch.shape) != (idx.shape[0],) + tuple(table.shape[1:]) \
+            or not batch.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {table.dtype} batch of shape "
+                         f"{(idx.shape[0],) + tuple(table.shape[1:])}, got {batch.dtype} {tuple(batch.shape)}")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1):
+        raise ValueError(f"{what}: n_bad must be one int32")
+    row_elems = table.numel() // table.shape[0]
+    if row_elems == 0:
+        raise ValueError(f"{what}: empty rows")
+    return table.shape[0], row_elems
+
+
+def rows_gather(table, idx, out=None, n_bad=None):
+    """out[i] = table[idx[i]] (sat_rows_gather): ``table`` [n_rows, ...] bf16 / fp32, ``idx`` int64 [n] on the device.
+    A row whose index lies outside the table comes out zero and adds 1 to ``n_bad`` (one int32 on the device, zeroed
+    by the caller) when that is given."""
+    if out is None:
+        L.require_device(table, idx)
+        out = torch.empty((idx.shape[0],) + tuple(table.shape[1:]), device=table.device, dtype=table.dtype)
+    n_rows, row_elems = _rows_args("rows_gather", table, idx, out, n_bad)
+    if idx.shape[0] == 0:   # an empty tensor has no pointer to hand over
+        return out
+    L.check(L.lib().sat_rows_gather(L.ptr(table), n_rows, row_elems, L.dtype_code(table.dtype), L.ptr(idx),
+                                    idx.shape[0], L.ptr(out), L.ptr(n_bad), L.stream_of(out)), "sat_rows_gather")
+    return out
+
+
+def rows_scatter(src, idx, table, n_bad=None):
+    """table[idx[i]] = src[i] (sat_rows_scatter), the indices distinct.  A row whose index lies outside the table is
+    skipped and adds 1 to ``n_bad`` when that is given."""
+    n_rows, row_elems = _rows_args("rows_scatter", table, idx, src, n_bad)
+    if idx.shape[0] == 0:
+        return table
+    L.check(L.lib().sat_rows_scatter(L.ptr(src), idx.shape[0], row_elems, L.dtype_code(table.dtype), L.ptr(idx),
+                                     L.ptr(table), n_rows, L.ptr(n_bad), L.stream_of(table)), "sat_rows_scatter")
+    return table
+
+
 def adam_step_(param, grad, exp_avg, exp_avg_sq, param_lp, beta1, beta2, eps, step_size, bc2_sqrt):
     L.check(L.lib().sat_adam_step(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), L.ptr(param_lp),
                                   param.numel(), beta1, beta2, eps, step_size, bc2_sqrt, L.stream_of(param)),

@@ -26,6 +26,13 @@ so it cannot be disabled, as in train.py:450), plus:
                   the block-5 convolutions, N <= 4) with --encoder-lr (default 1e-5) as a second Adam param group;
                   the frozen prefix of batch i+1 still runs ahead on the side stream, the tail runs inside the step;
                   each epoch also saves encoder_<network>_<epoch>.pth, which model_config.json then names
+  --cache-features  encode every unique image of each split once before epoch 1, keep the frozen trunk's output per
+                  image in HBM (sat_amd.FeatureCache) and train / evaluate from it: the loaders then open no image and
+                  a step gathers its rows with one launch.  With --fine-tune-encoder the cached tensor is the
+                  activation entering the trainable tail, which still runs inside the step.  Every rank holds the
+                  whole cache; a table that would leave less than FeatureCache's reserve of HBM free is refused
+  --feature-cache DIR  implies --cache-features; a valid cache file in DIR (same trunk prefix weights, key list,
+                  dtype, preprocessing) is loaded instead of filled, and a filled cache is written there (by rank 0)
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -75,8 +82,10 @@ class JsonCaptionDataset(torch.utils.data.Dataset):
     """The reference's on-disk layout (generate_json_data.py:51-63, dataset.py:15-52), loaded
     lazily per item (the reference decodes every image eagerly into RAM, which does not fit COCO)."""
 
-    def __init__(self, data_path, split_type="train", fraction=1.0, bert=False, decode_only=False):
+    def __init__(self, data_path, split_type="train", fraction=1.0, bert=False, decode_only=False,
+                 captions_only=False):
         self.decode_only = decode_only   # uint8 HWC at native size; resize + normalize run on the GPU
+        self.captions_only = captions_only   # (row index, caption, all captions): no image is opened (--cache-features)
         self.paths = json.load(open(os.path.join(data_path, f"{split_type}_img_paths.json")))
         name = f"{split_type}_captions_bert.json" if bert else f"{split_type}_captions.json"
         self.captions = json.load(open(os.path.join(data_path, name)))
@@ -92,10 +101,12 @@ class JsonCaptionDataset(torch.utils.data.Dataset):
         return len(self.paths)
 
     def __getitem__(self, i):
+        caps = torch.tensor(self.captions[i]), torch.tensor(self.all_captions[i])
+        if self.captions_only:
+            return (i,) + caps
         from PIL import Image
         with open(self.paths[i], "rb") as f:   # dataset.py:9-12
             img = Image.open(f).convert("RGB")
-        caps = torch.tensor(self.captions[i]), torch.tensor(self.all_captions[i])
         if self.decode_only:
             return (np.asarray(img, dtype=np.uint8),) + caps
         img = img.resize((224, 224), Image.BILINEAR)   # host transform (train.py:27-32), --host-preprocess
@@ -104,15 +115,18 @@ class JsonCaptionDataset(torch.utils.data.Dataset):
 
 
 class SyntheticDataset(torch.utils.data.Dataset):
-    def __init__(self, n, vocab, T, bert, seed):
+    def __init__(self, n, vocab, T, bert, seed, captions_only=False):
         g = torch.Generator().manual_seed(seed)
         self.caps = synthetic_captions(n, T, vocab, generator=g, bert=bert)
         self.seed = seed
+        self.captions_only = captions_only
 
     def __len__(self):
         return self.caps.shape[0]
 
     def __getitem__(self, i):
+        if self.captions_only:
+            return i, self.caps[i], self.caps[i:i + 1]
         g = torch.Generator().manual_seed(self.seed * 100003 + i)
         return synthetic_images(1, generator=g)[0], self.caps[i], self.caps[i:i + 1]
 
@@ -165,7 +179,15 @@ def parse(argv=None):
                    help="train the last N units of the trunk (resnet152: layer4's identity bottlenecks, N <= 2; "
                         "vgg19: the block-5 convolutions, N <= 4); 0 = frozen encoder")
     p.add_argument("--encoder-lr", type=float, default=1e-5, help="Adam learning rate of the trainable encoder units")
-    return p.parse_args(argv)
+    p.add_argument("--cache-features", action="store_true",
+                   help="encode every unique image once before epoch 1, keep the frozen trunk's output in HBM and "
+                        "train / evaluate from it (with --fine-tune-encoder: the activation entering the tail)")
+    p.add_argument("--feature-cache", type=str, default=None, metavar="DIR",
+                   help="implies --cache-features; load valid cache files from DIR, write them there after a fill")
+    args = p.parse_args(argv)
+    if args.feature_cache:
+        args.cache_features = True
+    return args
 
 
 def load_bert_embeddings(path):
@@ -233,15 +255,22 @@ class ShardSampler(torch.utils.data.Sampler):
         return len(self.idx)
 
 
-def loaders(args, split, rank, world):
+def make_dataset(args, split, captions_only=False):
     if args.synthetic:
-        ds = SyntheticDataset(args.synthetic if split == "train" else max(args.batch_size, args.synthetic // 8),
-                              args.vocab if not args.bert else sat_amd.Decoder.BERT_VOCAB,
-                              32 if args.bert else args.seq, args.bert, seed=args.seed * 10 + SPLIT_SEED[split])
-    else:
-        ds = JsonCaptionDataset(args.data, split, args.fraction, args.bert, decode_only=not args.host_preprocess)
+        return SyntheticDataset(args.synthetic if split == "train" else max(args.batch_size, args.synthetic // 8),
+                                args.vocab if not args.bert else sat_amd.Decoder.BERT_VOCAB,
+                                32 if args.bert else args.seq, args.bert, seed=args.seed * 10 + SPLIT_SEED[split],
+                                captions_only=captions_only)
+    return JsonCaptionDataset(args.data, split, args.fraction, args.bert, decode_only=not args.host_preprocess,
+                              captions_only=captions_only)
+
+
+def loaders(args, split, rank, world, captions_only=False):
+    """The split's loader.  ``captions_only``: its batches are (dataset rows, captions, all captions) and no worker
+    opens an image (the features come from a FeatureCache)."""
+    ds = make_dataset(args, split, captions_only)
     train = split == "train"
-    packed = not args.synthetic and not args.host_preprocess
+    packed = not args.synthetic and not args.host_preprocess and not captions_only
     if world > 1:
         sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True, seed=args.seed) \
             if train else ShardSampler(len(ds), rank, world)
@@ -249,7 +278,8 @@ def loaders(args, split, rank, world):
         sampler = None
     # train.py:76-88: the reference shuffles train only and keeps every validation / test batch
     return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=train and sampler is None,
-                                       sampler=sampler, num_workers=args.workers if not args.synthetic else 0,
+                                       sampler=sampler,
+                                       num_workers=args.workers if not (args.synthetic or captions_only) else 0,
                                        pin_memory=True, drop_last=train,
                                        collate_fn=sat_amd.collate_packed if packed else None)
 
@@ -298,16 +328,64 @@ def encoded_batches(loader, encoder, device, dt, max_steps, overlap):
         yield tail(pending)
 
 
-def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, log, grad_ar=None):
-    """train.py:119-192.  ``grad_ar``: a sat_amd.distributed.GradAllReduce for DP (N > 1)."""
+def preprocess_mode(args):
+    """How an image becomes the encoder's input: part of a cache file's key."""
+    return "synthetic" if args.synthetic else ("host" if args.host_preprocess else "device")
+
+
+def build_feature_cache(args, split, encoder, device, dt, rank, world, log):
+    """The split's FeatureCache: loaded from --feature-cache DIR when a valid file is there, else filled by one pass
+    over the split's unique images (and then written to DIR by rank 0).  Every rank holds the whole cache."""
+    t0 = time.time()
+    ds = make_dataset(args, split)
+    keys = ds.paths if hasattr(ds, "paths") else range(len(ds))
+    cache = sat_amd.FeatureCache(encoder, keys, dt, args.batch_size)
+    how = "loaded" if args.feature_cache and cache.load(args.feature_cache, split, preprocess_mode(args), device) \
+        else "built"
+    if how == "built":
+        packed = not args.synthetic and not args.host_preprocess
+        cache.fill(cache.image_loader(ds, 0 if args.synthetic else args.workers,
+                                      sat_amd.collate_packed if packed else None), device)
+    if args.feature_cache:
+        if world > 1:
+            dist.barrier()   # no rank still reads a file rank 0 is about to replace
+        if how == "built" and rank == 0:
+            cache.save(args.feature_cache, split, preprocess_mode(args))
+        if world > 1:
+            dist.barrier()
+    torch.cuda.synchronize(device)
+    log({"feature_cache": how, "split": split, "images": cache.n_images, "bytes": cache.nbytes,
+         "seconds": time.time() - t0})
+    return cache
+
+
+def cached_batches(loader, cache, encoder, device, dt, max_steps):
+    """(batch_idx, features, captions) of every batch, as encoded_batches yields them, from a captions-only loader
+    and a FeatureCache: one gather launch instead of the trunk.  A fine-tuned encoder's cache holds the activation
+    entering its tail, which runs here (under the caller's grad mode) as encoded_batches' tail() runs it."""
+    k = encoder.tail_start() if getattr(encoder, "_fine_tune", 0) else None
+    for batch_idx, (rows, captions, _) in enumerate(loader):
+        if max_steps and batch_idx >= max_steps:
+            break
+        feats = cache.gather(cache.slots[rows])
+        captions = captions.to(device, non_blocking=True)
+        if k is not None:
+            feats = encoder(feats, dtype=dt, steps=(k, encoder._plan_len()))
+        yield batch_idx, feats, captions
+
+
+def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, log, grad_ar=None, cache=None):
+    """train.py:119-192.  ``grad_ar``: a sat_amd.distributed.GradAllReduce for DP (N > 1).  ``cache``: the train
+    split's FeatureCache (``loader`` then is the captions-only one)."""
     encoder.eval()
     decoder.train()
     pad, skip = sat_amd.special_ids(args.bert)
     # the reference updates its meters every batch (train.py:179-181) with 4 host syncs per step; here
     # they accumulate on the device and are read once per log line
     meters = sat_amd.RunningMeters(device)
-    for batch_idx, feats, captions in encoded_batches(loader, encoder, device, dt, args.max_steps,
-                                                      not args.no_overlap):
+    batches = encoded_batches(loader, encoder, device, dt, args.max_steps, not args.no_overlap) if cache is None \
+        else cached_batches(loader, cache, encoder, device, dt, args.max_steps)
+    for batch_idx, feats, captions in batches:
         opt.zero_grad()
         preds, alphas = decoder(feats, captions)
         loss, metrics = sat_amd.caption_loss(preds, alphas, captions, args.alpha_c, pad, skip)
@@ -322,12 +400,15 @@ def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, l
             m = meters.read()
             log(dict(epoch=epoch, batch=batch_idx, train_loss=m["loss"], train_top1_acc=m["top1"],
                      train_top5_acc=m["top5"], train_loss_raw=m["loss_val"], train_tokens=m["count"]))
+    if cache is not None:
+        cache.check_bad_rows()   # the one host read of the gather kernel's bad-row count per epoch
     return meters.read()["loss"] if meters.last is not None else 0.0
 
 
-def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode, log):
+def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode, log, cache=None):
     """train.py:198-347 (teacher-forced greedy hypotheses, BLEU-1..4); with --beam-eval K also the BLEU of the
-    sentences batched beam search generates from the same features."""
+    sentences batched beam search generates from the same features.  ``cache``: the split's FeatureCache (``loader``
+    then is the captions-only one and its first item the dataset rows)."""
     encoder.eval()
     decoder.eval()
     pad, skip = sat_amd.special_ids(args.bert)
@@ -339,8 +420,14 @@ def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode,
         for batch_idx, (imgs, captions, all_caps) in enumerate(loader):
             if args.max_steps and batch_idx >= args.max_steps:
                 break
-            imgs, captions = imgs.to(device), captions.to(device)   # Tensor or PackedImages
-            feats = encoder(imgs, dtype=dt)
+            if cache is None:
+                imgs, captions = imgs.to(device), captions.to(device)   # Tensor or PackedImages
+                feats = encoder(imgs, dtype=dt)
+            else:
+                captions = captions.to(device)
+                feats = cache.gather(cache.slots[imgs])
+                if args.fine_tune_encoder:
+                    feats = encoder(feats, dtype=dt, steps=(encoder.tail_start(), encoder._plan_len()))
             preds, alphas = decoder(feats, captions)
             loss, metrics = sat_amd.caption_loss(preds, alphas, captions, args.alpha_c, pad, skip)
             m = sat_amd.StepMetrics(loss, metrics).values()
@@ -371,6 +458,8 @@ def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode,
     n = sums[3]
     avg = [v / n if n else 0.0 for v in sums[:3]]
     b1, b2, b3, b4 = bleu_mod.bleu_1_to_4(refs, hyps)
+    if cache is not None:
+        cache.check_bad_rows()
     rec = {"epoch": epoch, f"{mode}_loss": avg[0], f"{mode}_top1_acc": avg[1], f"{mode}_top5_acc": avg[2],
            f"{mode}_bleu1": b1, f"{mode}_bleu2": b2, f"{mode}_bleu3": b3, f"{mode}_bleu4": b4}
     if args.beam_eval > 0:
@@ -409,8 +498,12 @@ def main(argv=None):
         opt = sat_amd.Adam(decoder.parameters(), lr=args.lr)
     grad_ar = sat_dist.GradAllReduce(decoder) if world > 1 else None
     sched = torch.optim.lr_scheduler.StepLR(opt, args.step_size)
-    train_loader = loaders(args, "train", rank, world)
-    val_loader = loaders(args, "val", rank, world)
+    caches = {}
+    if args.cache_features:   # one pre-pass over each split's unique images (or a load), then loaders without images
+        for split in ("train", "val") + (("test",) if args.perform_test else ()):
+            caches[split] = build_feature_cache(args, split, encoder, device, dt, rank, world, log)
+    train_loader = loaders(args, "train", rank, world, captions_only=args.cache_features)
+    val_loader = loaders(args, "val", rank, world, captions_only=args.cache_features)
     os.makedirs(args.out, exist_ok=True)
     enc_path = os.path.join(args.out, f"encoder_{args.network}.pth")
     if rank == 0:   # the trunk this run uses, so generate_caption.py encodes with the same weights
@@ -419,8 +512,9 @@ def main(argv=None):
         t0 = time.time()
         if isinstance(getattr(train_loader, "sampler", None), torch.utils.data.distributed.DistributedSampler):
             train_loader.sampler.set_epoch(epoch)
-        train_epoch(epoch, encoder, decoder, opt, train_loader, args, device, dt, world, log, grad_ar)
-        evaluate(epoch, encoder, decoder, val_loader, args, device, dt, word_dict, "val", log)
+        train_epoch(epoch, encoder, decoder, opt, train_loader, args, device, dt, world, log, grad_ar,
+                    caches.get("train"))
+        evaluate(epoch, encoder, decoder, val_loader, args, device, dt, word_dict, "val", log, caches.get("val"))
         sched.step()
         if rank == 0:   # train.py:103-110
             torch.save(decoder.state_dict(), os.path.join(args.out, f"model_{args.network}_{epoch}.pth"))
@@ -438,8 +532,9 @@ def main(argv=None):
                 json.dump(cfg, f)
         log({"epoch": epoch, "epoch_seconds": time.time() - t0})
     if args.perform_test:
-        test_loader = loaders(args, "test", rank, world)
-        evaluate(args.epochs, encoder, decoder, test_loader, args, device, dt, word_dict, "test", log)
+        test_loader = loaders(args, "test", rank, world, captions_only=args.cache_features)
+        evaluate(args.epochs, encoder, decoder, test_loader, args, device, dt, word_dict, "test", log,
+                 caches.get("test"))
     if world > 1:
         dist.destroy_process_group()
 
