@@ -374,6 +374,22 @@ int sat_decoder_forward(const SatDecoderDims* d, const SatDecoderLayout* lay, co
                         const void* params_lp, const void* img_features, const int64_t* captions,
                         const uint8_t* dropout_mask, void* workspace, size_t workspace_bytes,
                         void* preds, float* alphas, int32_t* tokens, void* stream);
+/* Scheduled sampling (Bengio et al. 2015): sat_decoder_forward with the fed token chosen per row and step between
+ * the reference's two modes -- the ground-truth token (decoder.py:108-112) and the previous step's argmax
+ * (decoder.py:131-133).  Step 0 feeds the start token; at step t >= 1 row b feeds captions[b, t] where keep[b, t] = 1
+ * (an id outside [0, V) is clamped to 0, as the argmax id is) and argmax(preds[b, t-1]) (first index on ties) elsewhere.
+ *   keep = tf_mask[b, t] != 0 when tf_mask ([B, T-1] uint8, column 0 ignored) is given; otherwise the draw
+ *   u(seed, b, t) < p with u in [0, 1), p = *tf_prob_dev when tf_prob_dev is given (a device scalar read by the
+ *   kernels, so a captured graph follows a schedule) and tf_prob otherwise: p = 1 keeps every position, p = 0 none.
+ * The draw takes the dropout's seed (d->seed ^ f(*d->seed_ptr), the counter advanced once per training forward) under
+ * a domain constant of its own, and depends on (seed, b, t) only.  tf_mask_out (nullable, [B, T-1] uint8) receives
+ * the keep bits used, column 0 as 1.  Requires d->tf == 0 and 0 <= tf_prob <= 1 (SAT_ERR_INVALID otherwise); the
+ * workspace is that of d (tf == 0) and sat_decoder_backward runs on it unchanged: the fed tokens are constants. */
+int sat_decoder_forward_sampled(const SatDecoderDims* d, const SatDecoderLayout* lay, const float* params,
+                                const void* params_lp, const void* img_features, const int64_t* captions,
+                                const uint8_t* dropout_mask, float tf_prob, const float* tf_prob_dev,
+                                const uint8_t* tf_mask, uint8_t* tf_mask_out, void* workspace,
+                                size_t workspace_bytes, void* preds, float* alphas, int32_t* tokens, void* stream);
 /* phase 1 = output-head gradients only (f_out/f_h/f_z/deep_output), 2 = the rest
  * (needs phase 1 first), 3 = both.  accumulate=0 overwrites the active grads. */
 int sat_decoder_backward(const SatDecoderDims* d, const SatDecoderLayout* lay, const float* params,

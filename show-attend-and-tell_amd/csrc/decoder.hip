@@ -264,6 +264,41 @@ __global__ void start_tokens_kernel(int32_t* tok, int B, int T1, int start) {
   if (b < B) tok[(long)b * T1] = start;
 }
 
+// scheduled sampling (sat_decoder_forward_sampled), once per forward: every step's keep bit (mask or draw) and
+// pre[b, t] = the caption's token where it is set, -1 elsewhere; column 0: the start token, kept
+__global__ void tf_prefill_kernel(const int64_t* __restrict__ caps, int B, int T, int V, int start,
+                                  const uint8_t* __restrict__ keep_in, float p, const float* __restrict__ p_dev,
+                                  uint64_t seed, const uint64_t* __restrict__ seed_ptr, int32_t* __restrict__ pre,
+                                  uint8_t* __restrict__ keep_out) {
+  const int T1 = T - 1;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * T1) return;
+  const int b = i / T1, t = i - b * T1;
+  bool keep = true;
+  int tok = start;
+  if (t > 0) {
+    const int64_t c = caps[(long)b * T + t];
+    tok = (c < 0 || c >= V) ? 0 : (int)c;
+    if (keep_in) {
+      keep = keep_in[i] != 0;
+    } else {
+      if (seed_ptr) seed ^= *seed_ptr * 0xD1B54A32D192ED03ULL;
+      keep = sat_tf_uniform(seed, b, t) < (p_dev ? *p_dev : p);
+    }
+  }
+  pre[i] = keep ? tok : -1;
+  if (keep_out) keep_out[i] = keep ? 1 : 0;
+}
+
+// the per-call inputs of the sampled forward (nullptr: sat_decoder_forward's own paths)
+struct Sampled {
+  const int64_t* captions;
+  float p; const float* p_dev;
+  const uint8_t* mask; uint8_t* mask_out;
+};
+// the pre-resolved words [B, T-1] live in a backward-only region of the workspace (free during the forward)
+inline int32_t* tok_pre(const WS& w) { return (int32_t*)w.demb; }
+
 template <typename T>
 __global__ void ado_combine_rows_kernel(const float* fh, const float* fz, const T* emb, int rows, int E, long ld,
                                         T* comb) {
@@ -574,8 +609,9 @@ struct StepTimer {
 // writes its embedding row), against the per-op form's per-step embedding-half GEMM, dropout, f_z / f_h GEMMs, combine, vocabulary GEMM and
 // full-row argmax.  The embedding half of the gate GEMM depends only on the fed token, so it is one GEMM over the
 // vocabulary per forward (xt = emb W_ih[:, :E]^T + b_ih, once per weight version) and a row gather per step.
+// sm (scheduled sampling, nullable): the token fold selects per row between the caption's token and the argmax
 int greedy_loop(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, void* preds, const uint8_t* mask_in,
-                int32_t* tokens, hipStream_t s) {
+                int32_t* tokens, hipStream_t s, const Sampled* sm = nullptr) {
   const SatDecoderDims& d = c.d;
   const SatDecoderLayout& lay = c.lay;
   const int B = d.B, D = d.D, E = d.E, V = d.V, T1 = d.T - 1;
@@ -625,6 +661,7 @@ int greedy_loop(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, v
         l.am_val = w.am_val; l.am_idx = w.am_idx; l.am_ncb = sat_greedy_head_blocks(B, V, E); l.am_V = V;
         l.xt = w.xt; l.emb = c.F(lay.embedding); l.emb_t = c.at(w.emb_t, oE); l.emb_t_ld = c.T1 * E;
         l.tok_out = w.tok + t; l.tok_ld = T1;
+        if (sm) l.tok_pre = tok_pre(w) + t;
       }
       SAT_CHECK((hipError_t)sat_lstm_fwd_launch(l, s));
     }
@@ -763,10 +800,13 @@ extern "C" int sat_decoder_instance(const SatDecoderDims* dp, const SatDecoderLa
   return 0;
 }
 
-extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
-                                   const void* params_lp, const void* img_features, const int64_t* captions,
-                                   const uint8_t* dropout_mask, void* workspace, size_t workspace_bytes, void* preds,
-                                   float* alphas, int32_t* tokens, void* stream) {
+namespace {
+// sat_decoder_forward (sm == nullptr: every launch as before) and sat_decoder_forward_sampled (sm: d.tf == 0, the
+// greedy loops with the select form of the kernel that produces the fed token)
+int decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params, const void* params_lp,
+                    const void* img_features, const int64_t* captions, const uint8_t* dropout_mask, void* workspace,
+                    size_t workspace_bytes, void* preds, float* alphas, int32_t* tokens, void* stream,
+                    const Sampled* sm) {
   SAT_CHECK((hipError_t)check_dims(dp));
   SAT_REQUIRE(lay && params && img_features && captions && workspace && preds && alphas);
   SAT_REQUIRE(dp->dtype == SAT_F32 || params_lp);
@@ -793,6 +833,12 @@ extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLay
   } else {
     hipLaunchKernelGGL(start_tokens_kernel, dim3(sat_cdiv(B, 256)), dim3(256), 0, s, w.tok, B, T1, d.start_token);
     SAT_LAUNCH_CHECK();
+    if (sm) {
+      hipLaunchKernelGGL(tf_prefill_kernel, dim3(sat_cdiv(B * T1, 256)), dim3(256), 0, s, sm->captions, B, d.T, d.V,
+                         d.start_token, sm->mask, sm->p, sm->p_dev, d.seed, (const uint64_t*)d.seed_ptr, tok_pre(w),
+                         sm->mask_out);
+      SAT_LAUNCH_CHECK();
+    }
     SAT_CHECK((hipError_t)sat_embed_gather(c.F(lay->embedding), w.tok, B, 1, T1, E, d.dtype, w.emb_t, (long)T1 * E, s));
   }
   // init_lstm_state (decoder.py:137-147)
@@ -827,7 +873,7 @@ extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLay
     SAT_CHECK((hipError_t)linear(c, (int)c.R, 4 * E, E, w.emb_t, E, c.W(lay->wih), E + D, c.F(lay->bih), w.xg, 4 * E,
                                  SAT_F32, SAT_ACT_NONE, s));
 
-  if (greedy_fused(d)) return greedy_loop(c, w, sp, io, preds, dropout_mask, tokens, s);
+  if (greedy_fused(d)) return greedy_loop(c, w, sp, io, preds, dropout_mask, tokens, s, sm);
 
   for (int t = 0; t < T1; ++t) {
     if (!d.tf)
@@ -851,7 +897,12 @@ extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLay
     }
     if (!d.tf) {
       SAT_CHECK((hipError_t)head_forward(c, w, B, t, true, preds, dropout_mask, s));
-      if (t + 1 < T1)   // greedy feedback: argmax -> next token + its embedding (decoder.py:131-133)
+      if (t + 1 < T1 && sm)   // scheduled sampling: the caption's token where the row's keep bit is set
+        SAT_CHECK((hipError_t)sat_argmax_rows_select(c.at(preds, (long)t * d.V), d.dtype, (long)T1 * d.V, B, d.V,
+                                                     w.tok + t + 1, T1, c.F(lay->embedding), E,
+                                                     c.at(w.emb_t, (long)(t + 1) * E), (long)T1 * E,
+                                                     tok_pre(w) + t + 1, T1, s));
+      else if (t + 1 < T1)   // greedy feedback: argmax -> next token + its embedding (decoder.py:131-133)
         SAT_CHECK((hipError_t)sat_argmax_rows(c.at(preds, (long)t * d.V), d.dtype, (long)T1 * d.V, B, d.V,
                                               w.tok + t + 1, T1, c.F(lay->embedding), E,
                                               c.at(w.emb_t, (long)(t + 1) * E), (long)T1 * E, s));
@@ -861,6 +912,30 @@ extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLay
   if (d.training && d.seed_ptr) SAT_CHECK((hipError_t)sat_bump_seed(d.seed_ptr, s));
   if (tokens) SAT_CHECK(hipMemcpyAsync(tokens, w.tok, c.R * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   return 0;
+}
+}  // namespace
+
+extern "C" int sat_decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
+                                   const void* params_lp, const void* img_features, const int64_t* captions,
+                                   const uint8_t* dropout_mask, void* workspace, size_t workspace_bytes, void* preds,
+                                   float* alphas, int32_t* tokens, void* stream) {
+  return decoder_forward(dp, lay, params, params_lp, img_features, captions, dropout_mask, workspace, workspace_bytes,
+                         preds, alphas, tokens, stream, nullptr);
+}
+
+// Scheduled sampling (Bengio et al. 2015) between decoder.py:108-112 (the ground-truth token) and 131-133 (the
+// argmax): see sat_hip.h
+extern "C" int sat_decoder_forward_sampled(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
+                                           const void* params_lp, const void* img_features, const int64_t* captions,
+                                           const uint8_t* dropout_mask, float tf_prob, const float* tf_prob_dev,
+                                           const uint8_t* tf_mask, uint8_t* tf_mask_out, void* workspace,
+                                           size_t workspace_bytes, void* preds, float* alphas, int32_t* tokens,
+                                           void* stream) {
+  SAT_REQUIRE(dp && dp->tf == 0);
+  SAT_REQUIRE(tf_prob >= 0.f && tf_prob <= 1.f);   // also refuses NaN
+  const Sampled sm{captions, tf_prob, tf_prob_dev, tf_mask, tf_mask_out};
+  return decoder_forward(dp, lay, params, params_lp, img_features, captions, dropout_mask, workspace, workspace_bytes,
+                         preds, alphas, tokens, stream, &sm);
 }
 
 namespace {

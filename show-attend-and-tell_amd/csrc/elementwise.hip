@@ -607,13 +607,19 @@ __device__ __forceinline__ void am_wave_reduce(float& v, int& i) {
 // its 16-B vectors of a 256 x AM_NV x VEC-element pass before the first compare (the old
 // element-per-iteration loop waited out one load latency per element: 17.6 us per 128 x 10000 row
 // block), then a shuffle reduction per wave and one LDS exchange across the four waves.
+// SEL: scheduled sampling's select form (sat_argmax_rows_select): the row's pre-resolved word (decoder.hip
+// tf_prefill_kernel) is requested before the row scan, and the fed token is that word where it is >= 0, the argmax
+// elsewhere
 constexpr int AM_NV = 8;
-template <typename T, bool VECP>
+template <typename T, bool VECP, bool SEL = false>
 __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ X, long ld, int V, int32_t* __restrict__ out,
                                                      long out_stride, const float* __restrict__ emb, int E,
-                                                     T* __restrict__ emb_out, long emb_ld) {
+                                                     T* __restrict__ emb_out, long emb_ld,
+                                                     const int32_t* __restrict__ pre, long pre_stride) {
   constexpr int VEC = 16 / sizeof(T);
   const int b = blockIdx.x, tid = threadIdx.x;
+  int pre_tok = -1;
+  if (SEL) pre_tok = pre[(long)b * pre_stride];
   const T* row = X + (long)b * ld;
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -660,6 +666,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ X, lo
     if (am_better(sv[w], si[w], best, bi)) { best = sv[w]; bi = si[w]; }
   int id = bi;
   if (id < 0 || id >= V) id = 0;
+  if (SEL) id = (pre_tok >= 0 && pre_tok < V) ? pre_tok : id;
   if (tid == 0 && out) out[(long)b * out_stride] = id;
   if (emb_out) {
     const float* src = emb + (long)id * E;
@@ -865,11 +872,27 @@ int sat_argmax_rows(const void* X, int dtype, long ld, int B, int V, int32_t* ou
   const int esz = dtype == SAT_BF16 ? 2 : 4;
   const bool vec = ((uintptr_t)X & 15) == 0 && (ld * esz) % 16 == 0;
   if (dtype == SAT_BF16) {
-    if (vec) hipLaunchKernelGGL((argmax_kernel<bf16, true>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld);
-    else hipLaunchKernelGGL((argmax_kernel<bf16, false>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld);
+    if (vec) hipLaunchKernelGGL((argmax_kernel<bf16, true>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld, nullptr, 0);
+    else hipLaunchKernelGGL((argmax_kernel<bf16, false>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld, nullptr, 0);
   } else {
-    if (vec) hipLaunchKernelGGL((argmax_kernel<float, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld);
-    else hipLaunchKernelGGL((argmax_kernel<float, false>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld);
+    if (vec) hipLaunchKernelGGL((argmax_kernel<float, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, nullptr, 0);
+    else hipLaunchKernelGGL((argmax_kernel<float, false>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, nullptr, 0);
+  }
+  return (int)hipGetLastError();
+}
+
+int sat_argmax_rows_select(const void* X, int dtype, long ld, int B, int V, int32_t* out, long out_stride,
+                           const float* emb, int E, void* emb_out, long emb_ld, const int32_t* pre, long pre_stride,
+                           hipStream_t s) {
+  if (!pre) return (int)hipErrorInvalidValue;
+  const int esz = dtype == SAT_BF16 ? 2 : 4;
+  const bool vec = ((uintptr_t)X & 15) == 0 && (ld * esz) % 16 == 0;
+  if (dtype == SAT_BF16) {
+    if (vec) hipLaunchKernelGGL((argmax_kernel<bf16, true, true>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld, pre, pre_stride);
+    else hipLaunchKernelGGL((argmax_kernel<bf16, false, true>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld, pre, pre_stride);
+  } else {
+    if (vec) hipLaunchKernelGGL((argmax_kernel<float, true, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, pre, pre_stride);
+    else hipLaunchKernelGGL((argmax_kernel<float, false, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, pre, pre_stride);
   }
   return (int)hipGetLastError();
 }

@@ -32,7 +32,11 @@ __device__ __forceinline__ uint8_t dropout_keep(uint64_t seed, int b, int t, int
 // instance (with them in, its span went 3.5-3.7 -> 4.2 us per step, profiles/r6_s5 vs r6_s2)
 // HS, CS: the h and context products' split counts when compile-time (CS = 0 with HS > 0: no context part); HS = 0:
 // any counts, looped sums
-template <typename T, bool GREEDY, int HS, int CS>
+// SEL: scheduled sampling's select on the token fold (LstmFwdArgs::tok_pre), an instance of its own: the row's
+// pre-resolved word (the caption's token where its keep bit is set, -1 elsewhere) is requested with the other up-front
+// loads, the whole block still runs the argmax reduction and its barrier, and the winner is chosen after it -- no
+// extra dependent round trip
+template <typename T, bool GREEDY, int HS, int CS, bool SEL>
 __device__ __forceinline__ void lstm_fwd_gp_kernel_body(LstmFwdArgs a) {
   __shared__ float sg[4][64];
   __shared__ float am_v[4];
@@ -69,6 +73,10 @@ __device__ __forceinline__ void lstm_fwd_gp_kernel_body(LstmFwdArgs a) {
     int id = 0;
     if (GREEDY && a.am_val) {   // the token fold: the block's 64 units share one row (E % 64 == 0)
       const int br = (int)(base / E);
+      int pre = -1;   // a per-lane offset keeps the load a vector one, consumed after the reduction
+      if (SEL)
+        pre = (int)__builtin_amdgcn_raw_buffer_load_b32(sat_in_rsrc(a.tok_pre + (long)br * a.tok_ld, 4),
+                                                        (int)(ok ? 0u : kSatOOB), 0, 0);
       float best = -INFINITY;
       int bi = 0x7fffffff;
       for (int c = threadIdx.x; c < a.am_ncb; c += blockDim.x) {
@@ -89,6 +97,7 @@ __device__ __forceinline__ void lstm_fwd_gp_kernel_body(LstmFwdArgs a) {
       for (int w = 1; w < 4; ++w)
         if (sat_argmax_better(am_v[w], am_i[w], best, bi)) { best = am_v[w]; bi = am_i[w]; }
       id = (bi < 0 || bi >= a.am_V) ? 0 : bi;
+      if (SEL) id = (pre >= 0 && pre < a.am_V) ? pre : id;
       if (ok) xv = a.xt[(long)id * 4 * E + q * E + j];
     }
     if (ok) {
@@ -132,10 +141,10 @@ __device__ __forceinline__ void lstm_fwd_gp_kernel_body(LstmFwdArgs a) {
   }
 }
 
-template <typename T, bool GREEDY, int HS, int CS>
+template <typename T, bool GREEDY, int HS, int CS, bool SEL = false>
 __global__ __launch_bounds__(256) void lstm_fwd_gp_kernel(LstmFwdArgs a) {
   const SatStampT0 t0 = sat_stamp_begin(a.st);
-  lstm_fwd_gp_kernel_body<T, GREEDY, HS, CS>(a);
+  lstm_fwd_gp_kernel_body<T, GREEDY, HS, CS, SEL>(a);
   sat_stamp_end(a.st, t0);
 }
 
@@ -371,18 +380,18 @@ inline long lstm_blocks(int B, int E) {
   const long blocks = ((long)B * E + 63) / 64;
   return blocks > 4096 ? 4096 : blocks;
 }
-template <typename T, bool GREEDY, int HS>
+template <typename T, bool GREEDY, int HS, bool SEL = false>
 bool lstm_fwd_cs(int cs, dim3 grid, hipStream_t s, const LstmFwdArgs& a) {
   switch (cs) {   // the decoder's context-product split counts (0: no context part)
-    case 0: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 0>), grid, dim3(256), 0, s, a); return true;
-    case 1: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 1>), grid, dim3(256), 0, s, a); return true;
-    case 2: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 2>), grid, dim3(256), 0, s, a); return true;
-    case 4: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 4>), grid, dim3(256), 0, s, a); return true;
-    case 8: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 8>), grid, dim3(256), 0, s, a); return true;
+    case 0: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 0, SEL>), grid, dim3(256), 0, s, a); return true;
+    case 1: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 1, SEL>), grid, dim3(256), 0, s, a); return true;
+    case 2: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 2, SEL>), grid, dim3(256), 0, s, a); return true;
+    case 4: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 4, SEL>), grid, dim3(256), 0, s, a); return true;
+    case 8: hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, HS, 8, SEL>), grid, dim3(256), 0, s, a); return true;
     default: return false;
   }
 }
-template <typename T, bool GREEDY>
+template <typename T, bool GREEDY, bool SEL = false>
 void lstm_fwd_launch_t(dim3 grid, hipStream_t s, const LstmFwdArgs& a) {
   const int hs = a.h_splits < 1 ? 1 : a.h_splits, cs = a.cpart ? (a.c_splits < 1 ? 1 : a.c_splits) : 0;
   // the buffer resources of the compile-time forms address < 2 GiB
@@ -390,16 +399,21 @@ void lstm_fwd_launch_t(dim3 grid, hipStream_t s, const LstmFwdArgs& a) {
                     (!a.cpart || ((long)(cs - 1) * a.c_split_stride + (long)a.B * a.cpart_ld) * 4 < 0x7fffffffL) &&
                     (a.xt || ((long)a.B * a.xpart_ld) * 4 < 0x7fffffffL);
   if (sizeof(T) == 2 && fits) {
-    if (hs == 1 && lstm_fwd_cs<T, GREEDY, 1>(cs, grid, s, a)) return;
-    if (hs == 2 && lstm_fwd_cs<T, GREEDY, 2>(cs, grid, s, a)) return;
+    if (hs == 1 && lstm_fwd_cs<T, GREEDY, 1, SEL>(cs, grid, s, a)) return;
+    if (hs == 2 && lstm_fwd_cs<T, GREEDY, 2, SEL>(cs, grid, s, a)) return;
   }
-  hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, 0, 0>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((lstm_fwd_gp_kernel<T, GREEDY, 0, 0, SEL>), grid, dim3(256), 0, s, a);
 }
 int sat_lstm_fwd_launch(const LstmFwdArgs& args, hipStream_t s) {
   LstmFwdArgs a = args;
   a.st = sat_launch_stamps();
   const dim3 grid((unsigned)lstm_blocks(a.B, a.E));
   const bool greedy = a.hd_t || a.am_val;
+  if (a.tok_pre) {   // scheduled sampling: the fused greedy step's token fold only (bf16)
+    if (a.dtype != SAT_BF16 || !a.am_val) return (int)hipErrorInvalidValue;
+    lstm_fwd_launch_t<bf16, true, true>(grid, s, a);
+    return (int)hipGetLastError();
+  }
   if (a.dtype == SAT_BF16) {
     if (greedy) lstm_fwd_launch_t<bf16, true>(grid, s, a);
     else lstm_fwd_launch_t<bf16, false>(grid, s, a);

@@ -43,6 +43,27 @@ __device__ __forceinline__ bool sat_argmax_better(float x, int xi, float y, int 
   return x > y || (x == y && xi < yi);
 }
 
+// ---- scheduled sampling (sat_decoder_forward_sampled): which token row b feeds at step t >= 1 -- the caption's
+// (keep = 1) or the previous step's argmax (keep = 0).  keep comes from a given mask or from a draw u(seed, b, t) < p:
+// a function of (seed, b, t) only, with a domain constant of its own so it is not the dropout bit of the same (b, t).
+// Neither depends on the argmax, so one launch per forward (decoder.hip tf_prefill_kernel) resolves every step's keep bit and writes
+// pre[b, t] = the caption's token (an id outside [0, V) clamped to 0) where keep is set and -1 elsewhere; the kernels
+// that produce the fed token (the LSTM kernel's token fold, the argmax kernel) load that one word with their other
+// up-front loads and take it when it is >= 0.  Every workgroup of a row and both loop forms read the same word.
+constexpr uint64_t kSatTfDomain = 0x7F4A7C15F39CC060ULL;
+// u in [0, 1) with 24 bits, so p = 1 keeps every position and p = 0 none
+__device__ __forceinline__ float sat_tf_uniform(uint64_t seed, int b, int t) {
+  uint64_t x = (seed ^ kSatTfDomain) * 0x9E3779B97F4A7C15ULL + (((uint64_t)b << 40) ^ ((uint64_t)t << 20));
+  x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
+  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
+  x ^= x >> 33;
+  return (float)((uint32_t)x >> 8) * (1.0f / 16777216.0f);
+}
+// sat_argmax_rows whose row b takes pre[b * pre_stride] instead of its argmax when that is >= 0
+int sat_argmax_rows_select(const void* X, int dtype, long ld, int B, int V, int32_t* out, long out_stride,
+                           const float* emb, int E, void* emb_out, long emb_ld, const int32_t* pre, long pre_stride,
+                           hipStream_t s);
+
 // ---- deterministic dense embedding gradient (nn.Embedding backward = index_add over the fed tokens, decoder.py:87,
 // 133): G[tok[r], :] += dX[r, :] as per-token sums in row order (one sort launch + a segment-sum launch + a fix-up
 // launch for tokens whose rows span several pieces), no fp32 atomics.  R <= sat_embed_sorted_max_rows(), V < 2^18.
@@ -178,6 +199,10 @@ struct LstmFwdArgs {
   const float* xt; const float* emb; void* emb_t; long emb_t_ld;
   int32_t* tok_out; long tok_ld;
   SatStamps st;                         // in-kernel launch timestamps (set by the launcher)
+  // scheduled sampling (with the token fold only; nullptr: off): tok_pre[b * tok_ld] >= 0 is the token row b feeds
+  // (tf_prefill_kernel: the caption's, its keep bit set), < 0 leaves the fold's argmax; a separate kernel instance, the
+  // plain fold's code is unchanged
+  const int32_t* tok_pre;
 };
 int sat_lstm_fwd_launch(const LstmFwdArgs& a, hipStream_t s);
 

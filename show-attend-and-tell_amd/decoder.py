@@ -118,6 +118,28 @@ class Decoder(nn.Module):
         self._pending_bwd = None
         self.last_tokens = None        # int32 [B, T-1]: token fed at each step of the last forward
         self.record_tokens = True      # False: last_tokens stays None (training loops: no copy launch per step)
+        # scheduled sampling (training mode only; None = the reference's two modes, governed by use_tf): at every
+        # step t >= 1 a row feeds its caption's token with probability tf_prob and the previous step's argmax
+        # otherwise (sat_decoder_forward_sampled).  Eval mode ignores it.
+        self._tf_prob = None
+        self.tf_prob_tensor = None     # optional 1-element float32 device tensor read by the kernels instead of
+                                       # tf_prob: a captured step follows a decaying schedule without re-capture
+        self.tf_mask = None            # test hook: uint8 keep-mask [B, T-1] (column 0 ignored) instead of the draw
+        self.last_tf_mask = None       # uint8 [B, T-1]: the keep bits of the last sampled forward (record_tokens)
+
+    @property
+    def tf_prob(self):
+        return self._tf_prob
+
+    @tf_prob.setter
+    def tf_prob(self, p):
+        if p is not None:
+            if isinstance(p, bool) or not isinstance(p, (int, float)):
+                raise ValueError(f"tf_prob must be None or a float in [0, 1], got {p!r}")
+            p = float(p)
+            if not 0.0 <= p <= 1.0:   # also refuses NaN
+                raise ValueError(f"tf_prob must be None or a float in [0, 1], got {p!r}")
+        self._tf_prob = p
 
     # ------------------------------------------------------------------ layout
     def _groups(self):
@@ -476,6 +498,9 @@ class _DecoderFn(torch.autograd.Function):
     def forward(ctx, feats, captions, dec, *params):
         lib = L.lib()
         dims = dec._dims(feats, captions)
+        sampled = dec.tf_prob is not None and dec.training
+        if sampled:   # the greedy workspace and backward: the fed tokens are constants whichever source they have
+            dims.tf = 0
         lay = dec._layout()
         ws_bytes = lib.sat_decoder_workspace_bytes(ctypes.byref(dims))
         if ws_bytes == 0:
@@ -492,10 +517,30 @@ class _DecoderFn(torch.autograd.Function):
             if tuple(mask.shape) != (B, T1, dims.E):
                 raise ValueError(f"dropout_mask must be [B, T-1, E] = {(B, T1, dims.E)}")
         lp = dec._flat_lp if dims.dtype == L.SAT_BF16 else None
-        L.check(lib.sat_decoder_forward(ctypes.byref(dims), ctypes.byref(lay), L.ptr(dec._flat), L.ptr(lp),
-                                        L.ptr(feats), L.ptr(captions), L.ptr(mask), L.ptr(ws), ws_bytes,
-                                        L.ptr(preds), L.ptr(alphas), L.ptr(tokens), L.stream_of(preds)),
-                "sat_decoder_forward")
+        if sampled:
+            tf_mask = p_dev = None
+            if dec.tf_mask is not None:
+                if tuple(dec.tf_mask.shape) != (B, T1):
+                    raise ValueError(f"tf_mask must be [B, T-1] = {(B, T1)}")
+                tf_mask = dec.tf_mask.to(device=dev, dtype=torch.uint8).contiguous()
+            if dec.tf_prob_tensor is not None:
+                p_dev = dec.tf_prob_tensor
+                if p_dev.dtype != torch.float32 or p_dev.numel() != 1 or p_dev.device != dev:
+                    raise ValueError("tf_prob_tensor must be a 1-element float32 tensor on the features' device")
+            mask_out = torch.empty(B, T1, device=dev, dtype=torch.uint8) if dec.record_tokens else None
+            L.check(lib.sat_decoder_forward_sampled(ctypes.byref(dims), ctypes.byref(lay), L.ptr(dec._flat),
+                                                    L.ptr(lp), L.ptr(feats), L.ptr(captions), L.ptr(mask),
+                                                    dec.tf_prob, L.ptr(p_dev), L.ptr(tf_mask), L.ptr(mask_out),
+                                                    L.ptr(ws), ws_bytes, L.ptr(preds), L.ptr(alphas), L.ptr(tokens),
+                                                    L.stream_of(preds)),
+                    "sat_decoder_forward_sampled")
+            dec.last_tf_mask = mask_out
+        else:
+            L.check(lib.sat_decoder_forward(ctypes.byref(dims), ctypes.byref(lay), L.ptr(dec._flat), L.ptr(lp),
+                                            L.ptr(feats), L.ptr(captions), L.ptr(mask), L.ptr(ws), ws_bytes,
+                                            L.ptr(preds), L.ptr(alphas), L.ptr(tokens), L.stream_of(preds)),
+                    "sat_decoder_forward")
+            dec.last_tf_mask = None
         dec.last_tokens = tokens
         ctx.dec, ctx.dims, ctx.lay, ctx.ws, ctx.ws_bytes, ctx.lp = dec, dims, lay, ws, ws_bytes, lp
         ctx.save_for_backward(feats, preds, alphas)

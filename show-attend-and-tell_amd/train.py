@@ -33,6 +33,11 @@ so it cannot be disabled, as in train.py:450), plus:
                   whole cache; a table that would leave less than FeatureCache's reserve of HBM free is refused
   --feature-cache DIR  implies --cache-features; a valid cache file in DIR (same trunk prefix weights, key list,
                   dtype, preprocessing) is loaded instead of filled, and a filled cache is written there (by rank 0)
+  --tf-prob P     scheduled sampling (Bengio et al. 2015) while training: at every step a row feeds the ground-truth
+                  token with probability P and the model's own argmax of the previous step otherwise (seeded like the
+                  dropout masks, a different draw per rank); validation and test follow --tf as before
+  --tf-prob-end Q linear decay of that probability from P in epoch 1 to Q in the last epoch (default Q = P); the
+                  epoch's value is logged as tf_prob
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -184,10 +189,34 @@ def parse(argv=None):
                         "train / evaluate from it (with --fine-tune-encoder: the activation entering the tail)")
     p.add_argument("--feature-cache", type=str, default=None, metavar="DIR",
                    help="implies --cache-features; load valid cache files from DIR, write them there after a fill")
+    p.add_argument("--tf-prob", type=float, default=None, metavar="P",
+                   help="scheduled sampling: while training, every step feeds the ground-truth token with "
+                        "probability P and the model's own argmax otherwise (validation / test follow --tf)")
+    p.add_argument("--tf-prob-end", type=float, default=None, metavar="Q",
+                   help="with --tf-prob: linear decay from P in epoch 1 to Q in the last epoch (default: P)")
     args = p.parse_args(argv)
     if args.feature_cache:
         args.cache_features = True
+    if args.tf_prob is None:
+        if args.tf_prob_end is not None:
+            p.error("--tf-prob-end needs --tf-prob")
+    else:
+        if args.tf_prob_end is None:
+            args.tf_prob_end = args.tf_prob
+        for name, v in (("--tf-prob", args.tf_prob), ("--tf-prob-end", args.tf_prob_end)):
+            if not 0.0 <= v <= 1.0:
+                p.error(f"{name} must be in [0, 1]")
     return args
+
+
+def tf_prob_schedule(epoch, epochs, start, end):
+    """Teacher probability of ``epoch`` (1-based) of ``epochs``: linear from ``start`` in epoch 1 to ``end`` in the
+    last epoch (a single epoch trains at ``start``)."""
+    if epochs <= 1 or epoch <= 1:
+        return float(start)
+    if epoch >= epochs:
+        return float(end)
+    return float(start + (end - start) * (epoch - 1) / (epochs - 1))
 
 
 def load_bert_embeddings(path):
@@ -512,6 +541,8 @@ def main(argv=None):
         t0 = time.time()
         if isinstance(getattr(train_loader, "sampler", None), torch.utils.data.distributed.DistributedSampler):
             train_loader.sampler.set_epoch(epoch)
+        if args.tf_prob is not None:   # scheduled sampling: set once per epoch (eval mode ignores it)
+            decoder.tf_prob = tf_prob_schedule(epoch, args.epochs, args.tf_prob, args.tf_prob_end)
         train_epoch(epoch, encoder, decoder, opt, train_loader, args, device, dt, world, log, grad_ar,
                     caches.get("train"))
         evaluate(epoch, encoder, decoder, val_loader, args, device, dt, word_dict, "val", log, caches.get("val"))
@@ -530,7 +561,10 @@ def main(argv=None):
                     json.dump(word_dict, f)
             with open(os.path.join(args.out, "model_config.json"), "w") as f:
                 json.dump(cfg, f)
-        log({"epoch": epoch, "epoch_seconds": time.time() - t0})
+        rec = {"epoch": epoch, "epoch_seconds": time.time() - t0}
+        if args.tf_prob is not None:
+            rec["tf_prob"] = decoder.tf_prob
+        log(rec)
     if args.perform_test:
         test_loader = loaders(args, "test", rank, world, captions_only=args.cache_features)
         evaluate(args.epochs, encoder, decoder, test_loader, args, device, dt, word_dict, "test", log,
