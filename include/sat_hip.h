@@ -68,7 +68,8 @@ typedef struct {
                          * 1 for residual launches only, 2 fp32 tile staged in LDS */
   int split_gemm;       /* bf16 products with fp32 output and a k-major operand (the decoder's batched weight / input
                          * gradients; gemmsplit.hip: deterministic split-K, no atomics): 0 auto, 1 off (the tile
-                         * kernel), 2 128-row tiles only, 3 256-row tiles only */
+                         * kernel), 2 128-row tiles only, 3 256-row tiles only; 4 as 0 with every product launched on
+                         * its own (no grouped launches: the A/B of sat_gemm_group and the decoder backward's groups) */
   int split_k;          /* split_gemm: 0 the planner's split count, n > 0 exactly n splits when the shape allows */
   int attn_bwd;         /* attention backward per decoder step: 0 auto, 1 the two-launch form */
   int attn_bwd_chunks;  /* split attention backward: slot chunks per batch row (0 auto: ~256 workgroups) */
@@ -157,6 +158,40 @@ const char* sat_error_string(int code);
 /* --- generic building blocks -------------------------------------------- */
 int sat_gemm(const SatGemmArgs* args, void* stream);
 size_t sat_gemm_workspace_bytes(void);
+
+/* Independent products as one launch (the decoder backward's batched weight / input gradients; gemmsplit.hip).
+ * sat_gemm_group runs args[0 .. n) (n <= 8), each under its own args[i].policy: the products sat_gemm would run on
+ * the deterministic split-K kernel share one grid, planned jointly (tile height and split count per product;
+ * policy->split_gemm = 2 / 3 and policy->split_k force them as for sat_gemm, and a product in a group computes the
+ * same bits as sat_gemm with the same tile height and split count); the others run as sat_gemm would run them,
+ * after the group.  No product may read another's output.  workspace (device, >= sat_gemm_group_workspace_bytes();
+ * args[i].workspace is ignored): partial tiles and arrival tickets, the tickets zeroed by the call.
+ *
+ * sat_gemm_group_plan is the planner alone (host code, no device): shapes[i] with tile_rows (0, 128, 256) and splits
+ * (0 = the planner's) forced or free, the partial-tile bytes and the tickets the set may use.  plan[i] receives the
+ * product's tile height, split count, K range per split (kchunk), tile grid, its blocks [first_block, first_block
+ * + blocks) in the launch, and for splits > 1 its own slab region (bytes) and ticket range.  fallback = 1: the
+ * product is not in the launch (a forced split count the shape or the remaining workspace cannot hold) and runs on
+ * its own.  sat_gemm_group_block maps a block of the launch back to its work item (-1 product: none).
+ * sat_gemm_group_launches: grouped launches this process has issued so far, sat_gemm_group's and the decoder
+ * backward's (one captured into a graph counts once, at capture). */
+typedef struct {
+  int M, N, K;
+  int tile_rows, splits;
+} SatGemmGroupShape;
+typedef struct {
+  int tile_rows, splits, kchunk, tiles_m, tiles_n;
+  int first_block, blocks;
+  int64_t slab_offset, slab_bytes;
+  int ticket_offset, tickets;
+  int fallback;
+} SatGemmGroupPlan;
+int sat_gemm_group(const SatGemmArgs* args, int n, void* workspace, int64_t workspace_bytes, void* stream);
+size_t sat_gemm_group_workspace_bytes(void);
+int sat_gemm_group_plan(const SatGemmGroupShape* shapes, int n, int64_t slab_bytes, int tickets, SatGemmGroupPlan* plan);
+int sat_gemm_group_block(const SatGemmGroupPlan* plan, int n, int block, int* product, int* tile_m, int* tile_n,
+                         int* split);
+int64_t sat_gemm_group_launches(void);
 /* elementwise cast between SAT_F32 and SAT_BF16 storage (n elements). */
 int sat_cast(const void* x, int x_dtype, void* y, int y_dtype, int64_t n, void* stream);
 

@@ -57,6 +57,16 @@ class SatGemmArgs(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_int64)]
 
 
+class SatGemmGroupShape(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("M", "N", "K", "tile_rows", "splits")]
+
+
+class SatGemmGroupPlan(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("tile_rows", "splits", "kchunk", "tiles_m", "tiles_n", "first_block", "blocks")] + \
+               [("slab_offset", c_int64), ("slab_bytes", c_int64), ("ticket_offset", c_int), ("tickets", c_int),
+                ("fallback", c_int)]
+
+
 class SatDecoderDims(ctypes.Structure):
     _fields_ = [("B", c_int), ("L", c_int), ("D", c_int), ("E", c_int), ("V", c_int), ("T", c_int),
                 ("tf", c_int), ("ado", c_int), ("attention", c_int), ("bert", c_int), ("training", c_int),
@@ -87,6 +97,13 @@ _SIGNATURES = [
     ("sat_error_string", ctypes.c_char_p, [c_int]),
     ("sat_gemm", c_int, [ctypes.POINTER(SatGemmArgs), c_void_p]),
     ("sat_gemm_workspace_bytes", c_size_t, []),
+    ("sat_gemm_group", c_int, [ctypes.POINTER(SatGemmArgs), c_int, c_void_p, c_int64, c_void_p]),
+    ("sat_gemm_group_workspace_bytes", c_size_t, []),
+    ("sat_gemm_group_plan", c_int, [ctypes.POINTER(SatGemmGroupShape), c_int, c_int64, c_int,
+                                    ctypes.POINTER(SatGemmGroupPlan)]),
+    ("sat_gemm_group_block", c_int, [ctypes.POINTER(SatGemmGroupPlan), c_int, c_int, ctypes.POINTER(c_int),
+                                     ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    ("sat_gemm_group_launches", c_int64, []),
     ("sat_cast", c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]),
     ("sat_mean_rows_abi", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("sat_nchw_to_nhwc", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

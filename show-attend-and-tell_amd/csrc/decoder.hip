@@ -37,9 +37,14 @@ struct WS {
   unsigned* ticket;
   // deterministic split-K of the batched weight / input gradients (gemmsplit.hip): partial tiles, and
   // kTicketBlocks x kSatSplitTickets arrival tickets (each product of a backward phase has its own block, all zeroed
-  // by the phase's one zeroing launch)
+  // by the phase's one zeroing launch), then kGroups x kSatGroupTickets tickets of the backward's grouped launches
+  // (phase 1: group 0, phase 2: group 1), zeroed by the same launches
   float* gsplit;
   unsigned* gtickets;
+  // the grouped launches' partial tiles: every member keeps its single launch's split count (the same bits), so a
+  // group needs its members' slabs side by side (group_slab_bytes)
+  float* ggroup;
+  size_t ggroup_bytes;
   // the fused greedy step (greedy_fused): token table xt [V][4E] = emb W_ih[:, :E]^T + b_ih, the ado head's f_z
   // pre-activation slabs, the vocabulary head's per-block argmax partials
   float* xt;
@@ -50,6 +55,12 @@ struct WS {
   void* emb_ws;
 };
 constexpr int kTicketBlocks = 16;   // phase 1: blocks 0-7, phase 2: 8-15
+// The backward groups its products from this many rows B (T - 1) on; below, it issues them one by one in the order
+// it always had.  Measured at the bench shapes only: 3328 rows (B = 128) win 0.06-0.09 ms per step, 1664 rows
+// (B = 64) lose 0.03-0.05 ms, the set after the loop most; the threshold lies between the two and is
+// not resolved finer.
+constexpr int kGroupMinRows = 2560;
+constexpr int kGroups = 2;         // grouped launches: the head's four products (phase 1), those after the loop (phase 2)
 
 // split counts of the per-step skinny GEMMs (M = B rows).  bf16: the LDS-DMA kernel (128 x 64
 // tiles, 128 x 128 for k-major weights) with partial-output split-K -- aim for ~0.75 waves of
@@ -214,10 +225,19 @@ size_t carve(const SatDecoderDims& d, char* base, WS* w) {
   c.take(w->ticket, B * 4);
   if (d.dtype == SAT_BF16) {
     c.take(w->gsplit, sat_split_gemm_ws_bytes() - kSatSplitTickets * 4);
-    c.take(w->gtickets, (size_t)kTicketBlocks * kSatSplitTickets * 4);
+    c.take(w->gtickets, ((size_t)kTicketBlocks * kSatSplitTickets + (size_t)kGroups * kSatGroupTickets) * 4);
+    // the larger of the two groups (decoder_backward): the head's four products; those after the time loop
+    auto sb = [](size_t M, size_t N, size_t K) { return sat_gemm_group_slab_bound((int)M, (int)N, (int)K); };
+    const size_t four = sb(E, E, R) + sb(E, D, R) + sb(R, E, E) + sb(R, D, E);
+    const size_t post = sb(E, D, B * L) + sb(2 * E, D, B) + sb(HG, E, R) + sb(4 * E, E, R) + sb(4 * E, D, R) +
+                        sb(R, E, 4 * E);
+    w->ggroup_bytes = R >= (size_t)kGroupMinRows ? (four > post ? four : post) : 0;
+    c.take(w->ggroup, w->ggroup_bytes);
   } else {
     w->gsplit = nullptr;
     w->gtickets = nullptr;
+    w->ggroup = nullptr;
+    w->ggroup_bytes = 0;
   }
   c.take(w->demb, R * E * f);
   c.take(w->dpre0, B * 2 * E * f); c.take(w->dpre0_t, B * 2 * E * ts);
@@ -512,9 +532,9 @@ inline void use_split(SatGemm& g, const SplitWS* sw) {
 }
 
 // input gradient: Y[M,N] = X[M,K] W[K,N]   (W stored [K][N] row-major = torch weight [out,in])
-int dgrad_launch(const Ctx& c, int M, int N, int K, const void* X, long ldx, const void* Wt, long ldw, float* out,
-                 long ldo, hipStream_t s, const float* add1 = nullptr, long ld_add1 = 0, int splits = 0,
-                 long split_stride = 0, int a_tail = 0, const SplitWS* sw = nullptr) {
+SatGemm dgrad_gemm(const Ctx& c, int M, int N, int K, const void* X, long ldx, const void* Wt, long ldw, float* out,
+                   long ldo, const float* add1 = nullptr, long ld_add1 = 0, int splits = 0, long split_stride = 0,
+                   int a_tail = 0, const SplitWS* sw = nullptr) {
   SatGemm g;
   use_split(g, sw);
   g.a_tail = a_tail;
@@ -523,7 +543,13 @@ int dgrad_launch(const Ctx& c, int M, int N, int K, const void* X, long ldx, con
   g.A = X; g.lda = ldx; g.B = Wt; g.ldb = ldw; g.transB = 1;
   g.C = out; g.ldc = ldo; g.c_dtype = SAT_F32;
   g.add1 = add1; g.ld_add1 = ld_add1; g.add1_dtype = SAT_F32;
-  return sat_gemm_launch(g, s);
+  return g;
+}
+int dgrad_launch(const Ctx& c, int M, int N, int K, const void* X, long ldx, const void* Wt, long ldw, float* out,
+                 long ldo, hipStream_t s, const float* add1 = nullptr, long ld_add1 = 0, int splits = 0,
+                 long split_stride = 0, int a_tail = 0, const SplitWS* sw = nullptr) {
+  return sat_gemm_launch(dgrad_gemm(c, M, N, K, X, ldx, Wt, ldw, out, ldo, add1, ld_add1, splits, split_stride, a_tail,
+                                    sw), s);
 }
 
 // dL/d(gated context) = d gates . W_ih[:, E:]
@@ -994,6 +1020,22 @@ int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, cons
   const SatZeroSeg tickets_ph1{(float*)w.gtickets, 1, 8L * kSatSplitTickets, 8L * kSatSplitTickets};
   const SatZeroSeg tickets_ph2{(float*)w.gtickets + 8L * kSatSplitTickets, 1, 8L * kSatSplitTickets,
                                8L * kSatSplitTickets};
+  // Independent products of a phase run as one grid (gemmsplit.hip split_gemm_group_kernel): group k has tickets of
+  // its own behind the blocks (zeroed with its phase's) and the group slab, which the launches of a phase, ordered
+  // on the stream, share.  Every member keeps its single launch's split count, so the gradients are the single
+  // launches' bit for bit.  The products a group does not take (fp32 runs, shapes the split kernel refuses) keep
+  // their own launch and ticket block.  SatPolicy::split_gemm = 4: no groups (A/B).
+  unsigned* const group_tickets = w.gtickets ? w.gtickets + (long)kTicketBlocks * kSatSplitTickets : nullptr;
+  const SatZeroSeg gtickets_ph1{(float*)group_tickets, 1, kSatGroupTickets, kSatGroupTickets};
+  const SatZeroSeg gtickets_ph2{(float*)group_tickets + kSatGroupTickets, 1, kSatGroupTickets, kSatGroupTickets};
+  auto group = [&](int k, const SatGemm* gs, int n) {
+    return sat_gemm_group_launch(gs, nullptr, n, w.ggroup, (long)w.ggroup_bytes,
+                                 group_tickets ? group_tickets + (long)k * kSatGroupTickets : nullptr,
+                                 kSatGroupTickets, s, 1);
+  };
+  // below kGroupMinRows rows (no group slab carved) and under split_gemm = 4: one launch per product, in the order
+  // the backward always had
+  const bool grouping = w.ggroup_bytes > 0 && sat_policy().split_gemm != 4;
   auto wgs = [&](int blk, int M, int N, int K, const void* X, long ldx, const void* Y, long ldy, float* out, long ldo,
                  int a_tail = 0) {
     SatGemm g = wg(M, N, K, X, ldx, Y, ldy, out, ldo, a_tail);
@@ -1013,6 +1055,10 @@ int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, cons
   auto dgrad = [&](int blk, int M, int N, int K, const void* X, long ldx, const void* Wt, long ldw, float* out,
                    long ldo, const float* add1 = nullptr, long ld_add1 = 0) {
     return dgrad_launch(c, M, N, K, X, ldx, Wt, ldw, out, ldo, s, add1, ld_add1, 0, 0, 0, &sws[blk]);
+  };
+  auto dgg = [&](int blk, int M, int N, int K, const void* X, long ldx, const void* Wt, long ldw, float* out, long ldo,
+                 const float* add1 = nullptr, long ld_add1 = 0, int a_tail = 0) {
+    return dgrad_gemm(c, M, N, K, X, ldx, Wt, ldw, out, ldo, add1, ld_add1, 0, 0, a_tail, &sws[blk]);
   };
   auto colsum = [&](const void* X, int dt, long ld, int rows, int N, float* out, float* out2 = nullptr,
                     int cols_readable = 0) {
@@ -1040,25 +1086,35 @@ int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, cons
       SatGemm gfz = wgs(3, E, D, R, w.dfz_t, E, w.ctx_t, D, G(lay->fz_w), D);
       {
         SatGemm* gs[3] = {&gfo, &gfh, &gfz};
-        SatZeroSeg seg[4];
+        SatZeroSeg seg[5];
         int nseg = 0;
         if (w.gtickets) seg[nseg++] = tickets_ph1;
+        if (grouping) seg[nseg++] = gtickets_ph1;
         prezero(gs, 3, seg, nseg);
         SAT_CHECK((hipError_t)sat_zero_segs(seg, nseg, s));
       }
+      // dW f_out and dX f_out stay two launches: each fills the chip for ~60 us on its own, and grouped they gained
+      // 10 us alone and nothing in the step
       SAT_CHECK((hipError_t)sat_gemm_launch(gfo, s));
       SAT_CHECK((hipError_t)dgrad_launch(c, R, E, V, dpre, ldp, c.W(lay->fout_w), E, w.dcomb, E, s, nullptr, 0, 0, 0,
                                          VP != V, &sws[1]));
       SAT_CHECK((hipError_t)sat_ado_bwd_split(w.dcomb, w.fh, w.fz, (long)R * E, d.dtype, w.dfh_t, w.dfz_t, s));
-      SAT_CHECK((hipError_t)sat_gemm_launch(gfh, s));
-      SAT_CHECK((hipError_t)sat_gemm_launch(gfz, s));
       // the three bias gradients (column sums of d logits, d f_h, d f_z) in one launch pair
       const SatColsumSeg cs[3] = {{dpre, d.dtype, ldp, R, V, G(lay->fout_b), accumulate, nullptr, ldp != V},
                                   {w.dfh_t, d.dtype, E, R, E, G(lay->fh_b), accumulate, nullptr},
                                   {w.dfz_t, d.dtype, E, R, E, G(lay->fz_b), accumulate, nullptr}};
-      SAT_CHECK((hipError_t)sat_colsum_multi(cs, 3, w.colsum, s));
-      SAT_CHECK((hipError_t)dgrad(4, R, E, E, w.dfh_t, E, c.W(lay->fh_w), E, w.dhd, E));
-      if (att) SAT_CHECK((hipError_t)dgrad(5, R, D, E, w.dfz_t, E, c.W(lay->fz_w), D, w.dctx_head, D));
+      if (grouping) {   // the four products of d f_h and d f_z as one grid
+        const SatGemm four[4] = {gfh, gfz, dgg(4, R, E, E, w.dfh_t, E, c.W(lay->fh_w), E, w.dhd, E),
+                                 dgg(5, R, D, E, w.dfz_t, E, c.W(lay->fz_w), D, w.dctx_head, D)};
+        SAT_CHECK((hipError_t)group(0, four, att ? 4 : 3));
+        SAT_CHECK((hipError_t)sat_colsum_multi(cs, 3, w.colsum, s));
+      } else {
+        SAT_CHECK((hipError_t)sat_gemm_launch(gfh, s));
+        SAT_CHECK((hipError_t)sat_gemm_launch(gfz, s));
+        SAT_CHECK((hipError_t)sat_colsum_multi(cs, 3, w.colsum, s));
+        SAT_CHECK((hipError_t)dgrad(4, R, E, E, w.dfh_t, E, c.W(lay->fh_w), E, w.dhd, E));
+        if (att) SAT_CHECK((hipError_t)dgrad(5, R, D, E, w.dfz_t, E, c.W(lay->fz_w), D, w.dctx_head, D));
+      }
     } else {
       const void* dpre = d_preds;
       long ldp = (phase & 8) ? VP : V;
@@ -1105,6 +1161,7 @@ int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, cons
     }
     if (!d.bert && !accumulate) seg[nz++] = SatZeroSeg{G(lay->embedding), 1, (long)V * E, (long)V * E};
     if (w.gtickets) seg[nz++] = tickets_ph2;
+    if (grouping) seg[nz++] = gtickets_ph2;
     SatGemm* gs[5] = {&g_hcat, &g_wihx, &g_wihc, &g_init, &g_attw};
     prezero(gs, att ? 5 : 4, seg, nz);
     SAT_CHECK((hipError_t)sat_zero_segs(seg, nz, s));
@@ -1131,12 +1188,12 @@ int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, cons
   if (att) {
     SAT_CHECK((hipError_t)sat_attention_dws_launch(w.Ws, w.uh_all, w.de_all, c.F(lay->v_w), B, L, E, T1, d.dtype,
                                                    w.dWs_acc, w.dWs_t, s));
-    SAT_CHECK((hipError_t)sat_gemm_launch(g_attw, s));
+    if (!grouping) SAT_CHECK((hipError_t)sat_gemm_launch(g_attw, s));
   }
   // init_h / init_c (decoder.py:137-147): dh0 = dh_rec, dc0 = dc after the t = 0 step
   SAT_CHECK((hipError_t)sat_tanh_pair_bwd(w.dh_rec, sp.dh, (long)B * E, w.dc, w.hc0, B, E, w.dpre0, w.dpre0_t,
                                           d.dtype, s));
-  SAT_CHECK((hipError_t)sat_gemm_launch(g_init, s));
+  if (!grouping) SAT_CHECK((hipError_t)sat_gemm_launch(g_init, s));
   {   // every bias gradient of this phase (column sums) in one launch pair; b_hh and b_ih receive the same
       // gradient (the sum of d gates)
     SatColsumSeg cs[6];
@@ -1152,12 +1209,27 @@ int decoder_backward(const SatDecoderDims* dp, const SatDecoderLayout* lay, cons
     SAT_CHECK((hipError_t)sat_colsum_multi(cs, n, w.colsum, s));
   }
 
-  SAT_CHECK((hipError_t)sat_gemm_launch(g_hcat, s));
-  SAT_CHECK((hipError_t)sat_gemm_launch(g_wihx, s));
-  SAT_CHECK((hipError_t)sat_gemm_launch(g_wihc, s));
+  if (!grouping) {
+    SAT_CHECK((hipError_t)sat_gemm_launch(g_hcat, s));
+    SAT_CHECK((hipError_t)sat_gemm_launch(g_wihx, s));
+    SAT_CHECK((hipError_t)sat_gemm_launch(g_wihc, s));
+    if (!d.bert)
+      SAT_CHECK((hipError_t)dgrad(13, R, E, 4 * E, dg_t, HG, c.W(lay->wih), E + D, w.demb, E,
+                                  d.ado ? w.dcomb : nullptr, E));
+  } else {   // the weight gradients and the embedding's input gradient: independent of each other once the loop,
+             // the attention dWs and the init pre-activation gradients are done
+    SatGemm set[6];
+    int n = 0;
+    if (att) set[n++] = g_attw;
+    set[n++] = g_init;
+    set[n++] = g_hcat;
+    set[n++] = g_wihx;
+    set[n++] = g_wihc;
+    if (!d.bert)
+      set[n++] = dgg(13, R, E, 4 * E, dg_t, HG, c.W(lay->wih), E + D, w.demb, E, d.ado ? w.dcomb : nullptr, E);
+    SAT_CHECK((hipError_t)group(1, set, n));
+  }
   if (!d.bert) {  // dense embedding gradient (zeroed before the loop), scatter-added by fed token (decoder.py:87,133)
-    SAT_CHECK((hipError_t)dgrad(13, R, E, 4 * E, dg_t, HG, c.W(lay->wih), E + D, w.demb, E, d.ado ? w.dcomb : nullptr,
-                                E));
     if (w.emb_ws)
       SAT_CHECK((hipError_t)sat_embed_scatter_add_sorted(w.demb, w.tok, R, E, G(lay->embedding), accumulate, w.emb_ws,
                                                          s));

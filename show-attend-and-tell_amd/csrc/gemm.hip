@@ -467,15 +467,13 @@ SatPolicyScope::~SatPolicyScope() { t_policy = prev; }
 
 extern "C" size_t sat_gemm_workspace_bytes(void) { return sat_split_gemm_ws_bytes(); }
 
-extern "C" int sat_gemm(const SatGemmArgs* a, void* stream) {
-  SAT_REQUIRE(a != nullptr);
-  SatPolicyScope scope(a->policy);
+static SatGemm gemm_from_args(const SatGemmArgs* a, void* workspace, int64_t workspace_bytes) {
   SatGemm g;
-  if (a->workspace && a->workspace_bytes >= (int64_t)sat_split_gemm_ws_bytes()) {
+  if (workspace && workspace_bytes >= (int64_t)sat_split_gemm_ws_bytes()) {
     // [partial tiles | tickets]: the tickets are zeroed by the split launch itself (tickets_zeroed = 0)
-    g.split_ws = (float*)a->workspace;
+    g.split_ws = (float*)workspace;
     g.split_ws_bytes = (long)(sat_split_gemm_ws_bytes() - kSatSplitTickets * 4);
-    g.split_tickets = (unsigned*)((char*)a->workspace + g.split_ws_bytes);
+    g.split_tickets = (unsigned*)((char*)workspace + g.split_ws_bytes);
   }
   g.M = a->M; g.N = a->N; g.K = a->K; g.dtype = a->dtype;
   g.A = a->A; g.lda = a->lda; g.transA = a->transA;
@@ -484,7 +482,32 @@ extern "C" int sat_gemm(const SatGemmArgs* a, void* stream) {
   g.alpha = a->alpha; g.beta = a->beta; g.bias = a->bias;
   g.add1 = a->add1; g.ld_add1 = a->ld_add1; g.add1_dtype = a->add1_dtype;
   g.act = a->act; g.aux = a->aux; g.ld_aux = a->ld_aux; g.aux_dtype = a->aux_dtype;
-  return sat_gemm_launch(g, (hipStream_t)stream);
+  return g;
+}
+
+extern "C" int sat_gemm(const SatGemmArgs* a, void* stream) {
+  SAT_REQUIRE(a != nullptr);
+  SatPolicyScope scope(a->policy);
+  return sat_gemm_launch(gemm_from_args(a, a->workspace, a->workspace_bytes), (hipStream_t)stream);
+}
+
+// workspace: [partial tiles | kSatGroupTickets tickets].  Products that run on their own share the slab (the launches
+// are ordered on the stream) and take the first kSatSplitTickets tickets, zeroed by their own launch.
+extern "C" int sat_gemm_group(const SatGemmArgs* args, int n, void* workspace, int64_t workspace_bytes, void* stream) {
+  SAT_REQUIRE(args && n >= 1 && n <= kSatGemmGroupMax);
+  SAT_REQUIRE(workspace && workspace_bytes >= (int64_t)sat_gemm_group_workspace_bytes());
+  static_assert(kSatGroupTickets >= (int)kSatSplitTickets, "a product on its own finds its tickets in the group's");
+  const long slab_bytes = (long)(sat_split_gemm_ws_bytes() - kSatSplitTickets * 4);
+  unsigned* tickets = (unsigned*)((char*)workspace + slab_bytes);
+  SatGemm gs[kSatGemmGroupMax];
+  const SatPolicy* pol[kSatGemmGroupMax];
+  for (int i = 0; i < n; ++i) {
+    gs[i] = gemm_from_args(&args[i], workspace, (int64_t)sat_split_gemm_ws_bytes());
+    pol[i] = args[i].policy;
+  }
+  SAT_CHECK((hipError_t)sat_zero_rows((float*)tickets, kSatGroupTickets, 1, kSatGroupTickets, (hipStream_t)stream));
+  return sat_gemm_group_launch(gs, pol, n, (float*)workspace, slab_bytes, tickets, kSatGroupTickets,
+                               (hipStream_t)stream);
 }
 
 extern "C" int sat_conv2d_nhwc(const SatConvGeom* cg, int Cout, int dtype, const void* x, const void* w,

@@ -25,6 +25,15 @@
 //     acquire before its sc1 loads (cdna_hip_programming.md Guideline 16: a release / acquire pair under the memory
 //     model, besides the sc1 form MI355X_MICROARCH.md measures valid on its own);
 //   * XCD-aware order: the n-tiles of one (split, m-tile) panel share an XCD's L2.
+#include <algorithm>
+#include <atomic>
+#include <climits>
+#include <map>
+#include <mutex>
+#include <optional>
+#include <queue>
+#include <vector>
+
 #include "sat_common.h"
 #include "sat_internal.h"
 #include "sat_lds_pipe.h"
@@ -43,7 +52,7 @@
 #ifndef SAT_SPLIT_ACQUIRE
 #define SAT_SPLIT_ACQUIRE 0
 #endif
-#ifndef SAT_SPLIT_DEBUG     // diagnostics builds: 1 = record every ticket draw (tools/debug_split_tickets.py)
+#ifndef SAT_SPLIT_DEBUG    // diagnostics builds: 1 = record every ticket draw (tools/debug_split_tickets.py)
 #define SAT_SPLIT_DEBUG 0
 #endif
 #if SAT_SPLIT_DEBUG
@@ -91,28 +100,35 @@ struct SArgs {
   unsigned dbg_launch;    // SAT_SPLIT_DEBUG builds: launch number
 };
 
+// Block lin of a product's nwg = tiles_m x tiles_n x splits blocks -> its (m-tile, n-tile, split).  XCD-aware order
+// (cdna_hip_programming.md T1, bijective form): each XCD takes a contiguous run of (split, m-tile, n-tile) indices,
+// so the workgroups on one XCD share their A panel.  Host code (the planner's checks) shares the mapping.
+__host__ __device__ __forceinline__ void split_block_work(int lin, int nwg, int tiles_m, int tiles_n, int* mt, int* nt,
+                                                          int* split) {
+  const int q = nwg / 8, r = nwg % 8, x = lin % 8;
+  lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lin / 8;
+  *nt = lin % tiles_n;
+  const int rest = lin / tiles_n;
+  *mt = rest % tiles_m;
+  *split = rest / tiles_m;
+}
+
 __device__ __forceinline__ uint4 f4u(f32x4 v) {
   return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
 }
 
+// One workgroup's (tile, split) of product a: block lin of the product's nwg, on the caller's LDS ring smem
+// (SGeom<BM>::LDS bytes, 16-B aligned).
 template <int BM, bool AT, bool BT>
-__device__ __forceinline__ void split_gemm_body(const SArgs& a) {
+__device__ __forceinline__ void split_gemm_body(const SArgs& a, char* smem, int lin, const int nwg) {
   using G = SGeom<BM>;
   constexpr int MI = G::MI, NJ = G::NJ, AI = G::AI, BI = G::BI;
-  __shared__ __attribute__((aligned(16))) char smem[G::LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / G::WGN, wn = w % G::WGN;
 
-  int lin = blockIdx.x;
-  {   // XCD-aware order (cdna_hip_programming.md T1, bijective form): each XCD takes a contiguous run of
-      // (split, m-tile, n-tile) indices, so the workgroups on one XCD share their A panel
-    const int nwg = gridDim.x, q = nwg / 8, r = nwg % 8, x = lin % 8;
-    lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lin / 8;
-  }
-  const int nt = lin % a.tiles_n;
-  const int rest = lin / a.tiles_n;
-  const int mt = rest % a.tiles_m, split = rest / a.tiles_m;
+  int mt, nt, split;
+  split_block_work(lin, nwg, a.tiles_m, a.tiles_n, &mt, &nt, &split);
   const int m0 = mt * BM, n0 = nt * SBN;
   const int M = a.M, N = a.N;
   const int kbeg = split * a.kchunk, kend = min(a.K, kbeg + a.kchunk);
@@ -364,9 +380,47 @@ __device__ __forceinline__ void split_gemm_body(const SArgs& a) {
 
 template <int BM, bool AT, bool BT>
 __global__ __launch_bounds__(512) void split_gemm_kernel(SArgs a) {
+  __shared__ __attribute__((aligned(16))) char smem[SGeom<BM>::LDS];
   const SatStampT0 t0 = sat_stamp_begin(a.st);
-  split_gemm_body<BM, AT, BT>(a);
+  split_gemm_body<BM, AT, BT>(a, smem, blockIdx.x, gridDim.x);
   sat_stamp_end(a.st, t0);
+}
+
+// Up to kSatGemmGroupMax independent products in one grid: product i owns blocks [first[i], first[i] + blocks[i]) and
+// runs the body of its own (tile height, layouts) on its own slab region and ticket range.  The table travels in the
+// kernel arguments (no copy node, no memset node: a captured launch replays as it was recorded).  Products are laid
+// out longest work item first, so the long items start in the first round and the short ones fill the tail; within
+// a product the XCD-aware order holds as in a single launch (blocks of one residue mod 8 share an XCD whatever the
+// product's first block).  No workgroup waits for another: a grid of several rounds needs no co-residency.
+struct SGroupArgs {
+  SArgs p[kSatGemmGroupMax];
+  int first[kSatGemmGroupMax];    // first block; INT_MAX past the last product
+  int blocks[kSatGemmGroupMax];
+  int form[kSatGemmGroupMax];     // bit 0: B k-major, bit 1: A k-major, bit 2: 256-row tiles
+  SatStamps st;
+};
+
+__global__ __launch_bounds__(512) void split_gemm_group_kernel(SGroupArgs g) {
+  __shared__ __attribute__((aligned(16))) char smem[SGeom<256>::LDS];   // the taller tile's ring: one workgroup per CU
+  static_assert(SGeom<256>::LDS >= SGeom<128>::LDS && SGeom<128>::LDS > 80 * 1024, "either ring keeps a CU to itself");
+  const SatStampT0 t0 = sat_stamp_begin(g.st);
+  const int bi = blockIdx.x;
+  int idx = 0;   // wave-uniform: block index and table are scalar
+#pragma unroll
+  for (int i = 1; i < kSatGemmGroupMax; ++i) idx += bi >= g.first[i] ? 1 : 0;
+  const SArgs& a = g.p[idx];
+  const int lin = bi - g.first[idx], nwg = g.blocks[idx];
+  switch (g.form[idx]) {
+    case 0: split_gemm_body<128, false, false>(a, smem, lin, nwg); break;
+    case 1: split_gemm_body<128, false, true>(a, smem, lin, nwg); break;
+    case 2: split_gemm_body<128, true, false>(a, smem, lin, nwg); break;
+    case 3: split_gemm_body<128, true, true>(a, smem, lin, nwg); break;
+    case 4: split_gemm_body<256, false, false>(a, smem, lin, nwg); break;
+    case 5: split_gemm_body<256, false, true>(a, smem, lin, nwg); break;
+    case 6: split_gemm_body<256, true, false>(a, smem, lin, nwg); break;
+    default: split_gemm_body<256, true, true>(a, smem, lin, nwg); break;
+  }
+  sat_stamp_end(g.st, t0);
 }
 
 
@@ -434,8 +488,175 @@ bool split_eligible(const SatGemm& g) {
   const long c_bytes = 4L * ((long)(g.M - 1) * g.ldc + g.N);
   if (a_bytes >= (1L << 31) || b_bytes >= (1L << 31) || c_bytes >= (1L << 31)) return false;
   // auto: the long-K products (the weight gradients and the vocabulary / embedding input gradients)
-  if (mode == 0 && g.K < 512) return false;
+  if ((mode == 0 || mode == 4) && g.K < 512) return false;   // (4: auto, without grouped launches)
   return true;
+}
+
+// ---- the joint planner of a group launch ----
+// One grid of several rounds: the hardware hands blocks to CUs in block order as CUs free up, so the modelled time
+// of a set is the makespan of that list schedule over kSplitCUs CUs with the single launch's measured constants per
+// work item.  A split no longer has to fit one round (the last arriver of a tile never waits, so no co-residency is
+// needed); what remains per split are S <= kMaxSplits, >= 2 k-tiles per split, no empty split, and the set's slab
+// bytes and tickets.  Coordinate descent from (128-row tiles, unsplit): each product in turn takes the (tile
+// height, split count) that shortens the whole grid most, until a sweep changes nothing.
+struct GShape {
+  int M, N, K, bm, splits;   // bm, splits: 0 = the planner's, else forced
+};
+struct GItem {
+  int bm = 0, splits = 1, kchunk = 0, tiles_m = 0, tiles_n = 0, first = 0, blocks = 0;
+  long slab_off = 0, slab_bytes = 0;
+  int ticket_off = 0, tickets = 0, fallback = 0;
+};
+struct GOpt {
+  int b = 0, s = 1, kch = 0, nk = 0, tm = 0, tn = 0, tickets = 0;
+  long slab = 0;
+  long tiles() const { return (long)tm * tn; }
+  // modelled time of the work item of split j (the last split carries the K tail and, as the model's last arriver,
+  // the reads of the other partials).  Charging every split item its partial store as well made the planner's sets
+  // slower, alone and in the step, and was dropped.
+  double item_us(int j) const {
+    const int kt = kch < nk - j * kch ? kch : nk - j * kch;
+    return kt * kKtileUs[b] + kEpiUs + (s > 1 && j == s - 1 ? (s - 1) * kPartUs[b] : 0.0);
+  }
+};
+
+bool group_option(const GShape& sh, int b, int s, GOpt* o) {
+  const int nk = sat_cdiv(sh.K, SBK), bm = b ? 256 : 128;
+  if (s < 1 || s > kMaxSplits || (s > 1 && nk < 2 * s)) return false;
+  const int kch = sat_cdiv(nk, s);
+  if (sat_cdiv(nk, kch) != s) return false;   // no empty split
+  if (s > 1 && nk - (s - 1) * kch < 2) return false;   // the last split's tail too
+  o->b = b; o->s = s; o->kch = kch; o->nk = nk;
+  o->tm = sat_cdiv(sh.M, bm); o->tn = sat_cdiv(sh.N, SBN);
+  o->slab = s > 1 ? o->tiles() * s * bm * SBN * 4 : 0;
+  o->tickets = s > 1 ? (int)o->tiles() : 0;
+  return o->tiles() * s < (1L << 24);
+}
+
+// block order: products by the k-loop time of their work items, longest first (ties: the caller's order)
+void group_order(const GOpt* o, const int* in, int n, int* order) {
+  int m = 0;
+  for (int i = 0; i < n; ++i)
+    if (in[i]) order[m++] = i;
+  std::stable_sort(order, order + m,
+                   [&](int x, int y) { return o[x].kch * kKtileUs[o[x].b] > o[y].kch * kKtileUs[o[y].b]; });
+}
+
+double group_model_us(const GOpt* o, const int* in, int n) {
+  int order[kSatGemmGroupMax], m = 0;
+  for (int i = 0; i < n; ++i) m += in[i] ? 1 : 0;
+  group_order(o, in, n, order);
+  std::priority_queue<double, std::vector<double>, std::greater<double>> cu;
+  for (int i = 0; i < kSplitCUs; ++i) cu.push(0.0);
+  double end = 0;
+  for (int x = 0; x < m; ++x) {
+    const GOpt& p = o[order[x]];
+    for (int j = 0; j < p.s; ++j) {
+      const double us = p.item_us(j);
+      for (long t = 0; t < p.tiles(); ++t) {
+        const double e = cu.top() + us;
+        cu.pop();
+        cu.push(e);
+        end = e > end ? e : end;
+      }
+    }
+  }
+  return end;
+}
+
+void plan_group(const GShape* sh, int n, long slab_cap, long ticket_cap, GItem* out) {
+  GOpt cur[kSatGemmGroupMax];
+  int in[kSatGemmGroupMax];
+  long slab = 0, tickets = 0;
+  // forced split counts first (the caller's order): one the shape cannot hold, or whose region does not fit what is
+  // left, falls back to a launch of its own
+  for (int i = 0; i < n; ++i) {
+    out[i] = GItem{};
+    in[i] = 1;
+    if (sh[i].splits > 0) {
+      if (!group_option(sh[i], sh[i].bm == 256, sh[i].splits, &cur[i]) || slab + cur[i].slab > slab_cap ||
+          tickets + cur[i].tickets > ticket_cap) {
+        in[i] = 0;
+        continue;
+      }
+      slab += cur[i].slab;
+      tickets += cur[i].tickets;
+    } else if (!group_option(sh[i], sh[i].bm == 256, 1, &cur[i])) {
+      in[i] = 0;
+    }
+  }
+  // with a forced split count and a free tile height, the height is chosen below at that count
+  double best = group_model_us(cur, in, n);
+  for (int sweep = 0; sweep < 4; ++sweep) {
+    bool changed = false;
+    for (int i = 0; i < n; ++i) {
+      if (!in[i] || (sh[i].splits > 0 && sh[i].bm > 0)) continue;
+      const GOpt keep = cur[i];
+      GOpt pick = keep;
+      for (int b = 0; b < 2; ++b) {
+        if (sh[i].bm > 0 && (sh[i].bm == 256) != (b == 1)) continue;
+        for (int s = 1; s <= kMaxSplits; ++s) {
+          if (sh[i].splits > 0 && s != sh[i].splits) continue;
+          GOpt o;
+          if (!group_option(sh[i], b, s, &o)) continue;
+          if (slab - keep.slab + o.slab > slab_cap || tickets - keep.tickets + o.tickets > ticket_cap) continue;
+          cur[i] = o;
+          const double us = group_model_us(cur, in, n);
+          if (us < best - 1e-9) {
+            best = us;
+            pick = o;
+          }
+        }
+      }
+      cur[i] = pick;
+      if (pick.b != keep.b || pick.s != keep.s) {
+        slab += pick.slab - keep.slab;
+        tickets += pick.tickets - keep.tickets;
+        changed = true;
+      }
+    }
+    if (!changed) break;
+  }
+  int order[kSatGemmGroupMax], m = 0;
+  for (int i = 0; i < n; ++i) m += in[i] ? 1 : 0;
+  group_order(cur, in, n, order);
+  int first = 0;
+  for (int x = 0; x < m; ++x) {
+    GItem& it = out[order[x]];
+    const GOpt& p = cur[order[x]];
+    it.bm = p.b ? 256 : 128; it.splits = p.s; it.kchunk = p.kch * SBK; it.tiles_m = p.tm; it.tiles_n = p.tn;
+    it.first = first;
+    it.blocks = (int)(p.tiles() * p.s);
+    first += it.blocks;
+  }
+  long so = 0;
+  int to = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!in[i]) {
+      out[i].fallback = 1;
+      continue;
+    }
+    out[i].slab_off = so; out[i].slab_bytes = cur[i].slab;
+    out[i].ticket_off = to; out[i].tickets = cur[i].tickets;
+    so += cur[i].slab;
+    to += cur[i].tickets;
+  }
+}
+
+// plans are pure functions of the shapes and capacities: kept, so an eager backward plans each set once
+void plan_group_cached(const GShape* sh, int n, long slab_cap, long ticket_cap, GItem* out) {
+  static std::mutex mu;
+  static std::map<std::vector<long>, std::vector<GItem>> cache;
+  std::vector<long> key{n, slab_cap, ticket_cap};
+  for (int i = 0; i < n; ++i) key.insert(key.end(), {sh[i].M, sh[i].N, sh[i].K, sh[i].bm, sh[i].splits});
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(key);
+  if (it == cache.end()) {
+    std::vector<GItem> v(n);
+    plan_group(sh, n, slab_cap, ticket_cap, v.data());
+    it = cache.emplace(key, v).first;
+  }
+  for (int i = 0; i < n; ++i) out[i] = it->second[i];
 }
 
 }  // namespace
@@ -457,12 +678,8 @@ static bool split_takes(const SatGemm& g) {
 
 int sat_split_gemm_takes(const SatGemm& g) { return split_takes(g) ? 1 : 0; }
 
-int sat_split_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
-  *err = 0;
-  if (!split_takes(g)) return 0;
-  const bool have_ws = g.split_ws && g.split_tickets;
-  const SPlan p = plan_split(g, have_ws);
-  if (p.bm == 0) return 0;
+// the kernel's view of g under a plan (slab, tickets and stamps are the launch's to fill)
+static SArgs split_args(const SatGemm& g, int splits, int kchunk, int tiles_m, int tiles_n) {
   const bool at = g.transA != 0, bt = g.transB != 0;
   SArgs a{};
   a.M = g.M; a.N = g.N; a.K = g.K;
@@ -470,13 +687,24 @@ int sat_split_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
   a.C = (float*)g.C; a.ldc = g.ldc;
   a.beta1 = g.beta != 0.f;
   a.add1 = (const float*)g.add1; a.ld_add1 = g.ld_add1;
-  a.splits = p.splits; a.kchunk = p.kchunk;
+  a.splits = splits; a.kchunk = kchunk;
   a.a_mlim = at && g.a_tail ? sat_cdiv(g.M, 8) * 8 : g.M;
-  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
+  a.tiles_m = tiles_m; a.tiles_n = tiles_n;
   a.a_bytes = (unsigned)(at ? 2L * ((long)(g.K - 1) * g.lda + a.a_mlim)
                             : 2L * ((long)(g.M - 1) * g.lda + sat_cdiv(g.K, 8) * 8));
   a.b_bytes = (unsigned)(bt ? 2L * ((long)(g.K - 1) * g.ldb + g.N) : 2L * ((long)(g.N - 1) * g.ldb + g.K));
   a.c_bytes = (unsigned)(4L * ((long)(g.M - 1) * g.ldc + g.N));
+  return a;
+}
+
+int sat_split_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
+  *err = 0;
+  if (!split_takes(g)) return 0;
+  const bool have_ws = g.split_ws && g.split_tickets;
+  const SPlan p = plan_split(g, have_ws);
+  if (p.bm == 0) return 0;
+  const bool at = g.transA != 0, bt = g.transB != 0;
+  SArgs a = split_args(g, p.splits, p.kchunk, p.tiles_m, p.tiles_n);
   if (p.splits > 1) {
     const long slab = (long)p.tiles_m * p.tiles_n * p.splits * p.bm * SBN * 4;
     SAT_REQUIRE(slab <= g.split_ws_bytes && (long)p.tiles_m * p.tiles_n <= kSplitCUs);
@@ -504,6 +732,133 @@ int sat_split_gemm_try(const SatGemm& g, hipStream_t s, int* err) {
   }
   *err = (int)hipGetLastError();
   return 1;
+}
+
+static std::atomic<int64_t> g_group_launches{0};   // sat_gemm_group_launches
+
+// SatPolicy::split_gemm = 4: the planner's choices with every product launched on its own (the A/B of the groups).
+// keep_splits: every member keeps the split count of its single launch (plan_split), so its fp32 sums run over the
+// same K ranges in the same order and the group writes the single launches' bits; the joint planner then chooses
+// the tile heights (which do not enter the sum order: each output element adds its k-tiles in k order under either
+// height), the block order and the regions.
+int sat_gemm_group_launch(const SatGemm* gs, const SatPolicy* const* pol, int n, float* slab, long slab_bytes,
+                          unsigned* tickets, int n_tickets, hipStream_t s, int keep_splits) {
+  SAT_REQUIRE(gs && n >= 0 && n <= kSatGemmGroupMax);
+  GShape sh[kSatGemmGroupMax];
+  int idx[kSatGemmGroupMax], m = 0;   // members: what a launch of its own would run on the split kernel
+  for (int i = 0; i < n; ++i) {
+    std::optional<SatPolicyScope> scope;
+    if (pol) scope.emplace(pol[i]);
+    const SatPolicy& p = sat_policy();
+    if (!slab || !tickets || p.split_gemm == 4 || gs[i].M <= 0 || gs[i].N <= 0 || sat_skinny_takes(gs[i]) ||
+        !split_eligible(gs[i]))
+      continue;
+    sh[m] = GShape{gs[i].M, gs[i].N, gs[i].K, p.split_gemm == 2 ? 128 : p.split_gemm == 3 ? 256 : 0,
+                   p.split_k > 0 ? p.split_k : 0};
+    if (keep_splits) {
+      const SPlan single = plan_split(gs[i], gs[i].split_ws && gs[i].split_tickets);
+      if (single.bm == 0) continue;   // no plan under this policy: not this kernel's, as for a launch of its own
+      sh[m].splits = single.splits;
+    }
+    idx[m++] = i;
+  }
+  GItem plan[kSatGemmGroupMax];
+  bool grouped[kSatGemmGroupMax] = {};
+  if (m >= 2) plan_group_cached(sh, m, slab_bytes, n_tickets, plan);   // a group of one is a single launch
+  int members = 0;
+  for (int x = 0; m >= 2 && x < m; ++x) members += plan[x].fallback ? 0 : 1;
+  if (members >= 2) {
+    SGroupArgs ga{};
+    int total = 0;
+    for (int x = 0, k = 0; x < m; ++x) {
+      const GItem& it = plan[x];
+      if (it.fallback) continue;
+      const SatGemm& g = gs[idx[x]];
+      grouped[idx[x]] = true;
+      SArgs& a = ga.p[k];
+      a = split_args(g, it.splits, it.kchunk, it.tiles_m, it.tiles_n);
+      if (it.splits > 1) {
+        SAT_REQUIRE(it.slab_off + it.slab_bytes <= slab_bytes && it.ticket_off + it.tickets <= n_tickets);
+        a.slab = slab + it.slab_off / 4; a.slab_bytes = (unsigned)it.slab_bytes;
+        a.tickets = tickets + it.ticket_off;
+      }
+#if SAT_SPLIT_DEBUG
+      a.dbg_launch = ++g_sdbg_launch;
+#endif
+      ga.first[k] = it.first; ga.blocks[k] = it.blocks;
+      ga.form[k] = (it.bm == 256 ? 4 : 0) | (g.transA ? 2 : 0) | (g.transB ? 1 : 0);
+      total += it.blocks;
+      ++k;
+    }
+    // the table in block order, so the search for a block's product is a count of first[] <= block
+    for (int x = 1; x < members; ++x)
+      for (int y = x; y > 0 && ga.first[y] < ga.first[y - 1]; --y) {
+        std::swap(ga.p[y], ga.p[y - 1]);
+        std::swap(ga.first[y], ga.first[y - 1]);
+        std::swap(ga.blocks[y], ga.blocks[y - 1]);
+        std::swap(ga.form[y], ga.form[y - 1]);
+      }
+    for (int k = members; k < kSatGemmGroupMax; ++k) ga.first[k] = INT_MAX;
+    ga.st = sat_launch_stamps();
+    hipLaunchKernelGGL(split_gemm_group_kernel, dim3((unsigned)total), dim3(512), 0, s, ga);
+    SAT_CHECK(hipGetLastError());
+    g_group_launches.fetch_add(1, std::memory_order_relaxed);
+  }
+  for (int i = 0; i < n; ++i) {
+    if (grouped[i]) continue;
+    std::optional<SatPolicyScope> scope;
+    if (pol) scope.emplace(pol[i]);
+    SAT_CHECK((hipError_t)sat_gemm_launch(gs[i], s));
+  }
+  return 0;
+}
+
+extern "C" int sat_gemm_group_plan(const SatGemmGroupShape* shapes, int n, int64_t slab_bytes, int tickets,
+                                   SatGemmGroupPlan* plan) {
+  SAT_REQUIRE(shapes && plan && n >= 1 && n <= kSatGemmGroupMax && slab_bytes >= 0 && tickets >= 0);
+  GShape sh[kSatGemmGroupMax];
+  for (int i = 0; i < n; ++i) {
+    SAT_REQUIRE(shapes[i].M > 0 && shapes[i].N > 0 && shapes[i].K > 0 && shapes[i].splits >= 0 &&
+                (shapes[i].tile_rows == 0 || shapes[i].tile_rows == 128 || shapes[i].tile_rows == 256));
+    sh[i] = GShape{shapes[i].M, shapes[i].N, shapes[i].K, shapes[i].tile_rows, shapes[i].splits};
+  }
+  GItem it[kSatGemmGroupMax];
+  plan_group(sh, n, slab_bytes, tickets, it);
+  for (int i = 0; i < n; ++i)
+    plan[i] = SatGemmGroupPlan{it[i].bm, it[i].splits, it[i].kchunk, it[i].tiles_m, it[i].tiles_n, it[i].first,
+                               it[i].blocks, it[i].slab_off, it[i].slab_bytes, it[i].ticket_off, it[i].tickets,
+                               it[i].fallback};
+  return 0;
+}
+
+extern "C" int sat_gemm_group_block(const SatGemmGroupPlan* plan, int n, int block, int* product, int* tile_m,
+                                    int* tile_n, int* split) {
+  SAT_REQUIRE(plan && product && tile_m && tile_n && split && n >= 1 && n <= kSatGemmGroupMax);
+  *product = -1;
+  for (int i = 0; i < n; ++i)
+    if (!plan[i].fallback && block >= plan[i].first_block && block < plan[i].first_block + plan[i].blocks) {
+      *product = i;
+      split_block_work(block - plan[i].first_block, plan[i].blocks, plan[i].tiles_m, plan[i].tiles_n, tile_m, tile_n,
+                       split);
+    }
+  return 0;
+}
+
+size_t sat_gemm_group_slab_bound(int M, int N, int K) {
+  // plan_split under any policy: S <= kMaxSplits, >= 2 k-tiles per split, and tiles x S <= kSplitCUs at its tile
+  // height -- most splits with 256-row tiles, which are the fewest; the group's other tile height at the same S
+  // needs no more bytes (cdiv(M, 128) x 128 <= cdiv(M, 256) x 256)
+  const long tiles = (long)sat_cdiv(M, 256) * sat_cdiv(N, SBN);
+  if (tiles < 1) return 0;
+  long s = kSplitCUs / tiles < kMaxSplits ? kSplitCUs / tiles : kMaxSplits;
+  if (s > sat_cdiv(K, SBK) / 2) s = sat_cdiv(K, SBK) / 2;
+  return s > 1 ? (size_t)(tiles * s) * 256 * SBN * 4 : 0;
+}
+
+extern "C" int64_t sat_gemm_group_launches(void) { return g_group_launches.load(std::memory_order_relaxed); }
+
+extern "C" size_t sat_gemm_group_workspace_bytes(void) {
+  return sat_split_gemm_ws_bytes() - kSatSplitTickets * 4 + (size_t)kSatGroupTickets * 4;
 }
 
 #if SAT_SPLIT_DEBUG

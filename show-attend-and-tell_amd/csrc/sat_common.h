@@ -215,6 +215,20 @@ int sat_split_gemm_try(const SatGemm& g, hipStream_t s, int* err);
 int sat_split_gemm_takes(const SatGemm& g);
 size_t sat_split_gemm_ws_bytes();
 constexpr size_t kSatSplitTickets = 256;   // tickets one split launch may use
+// Independent products of that kernel as one grid (gemmsplit.hip split_gemm_group_kernel).  gs[i] runs under pol[i]
+// (pol nullable: the caller's policy for all).  The members -- what sat_gemm_launch would hand to the split kernel
+// -- share one launch, planned jointly, with slab regions inside [slab, slab + slab_bytes) and ticket ranges inside
+// [tickets, tickets + n_tickets), which the caller has zeroed; every other product, and a member whose forced split
+// does not fit, is launched on its own by sat_gemm_launch afterwards (its own split_ws / split_tickets).
+constexpr int kSatGemmGroupMax = 8;
+constexpr int kSatGroupTickets = 1024;     // tickets one group launch may use
+// keep_splits: every member keeps its single launch's split count, so the group writes the single launches' bits
+// (the decoder backward); 0: the joint planner chooses the split counts too.  sat_gemm_group_slab_bound: partial-tile
+// bytes that hold an M x N x K product of a keep_splits group under any policy (a single launch splits only while
+// tiles x splits fit one round of 256 workgroups and every split has two k-tiles).
+int sat_gemm_group_launch(const SatGemm* gs, const SatPolicy* const* pol, int n, float* slab, long slab_bytes,
+                          unsigned* tickets, int n_tickets, hipStream_t s, int keep_splits = 0);
+size_t sat_gemm_group_slab_bound(int M, int N, int K);
 // 256x128 pipelined bf16 conv / NT GEMM (convpipe.hip); returns 1 when it launched.
 int sat_conv_pipe_try(const SatGemm& g, hipStream_t s, int* err);
 // weight-stationary streaming kernel for K <= 512 1x1 convs (convstream.hip); returns 1 when it launched.
@@ -222,6 +236,7 @@ int sat_conv_stream_try(const SatGemm& g, hipStream_t s, int* err);
 // register-direct skinny GEMM (M <= 128, NT, fp32 / partial-slab output: the decoder's per-step
 // products, skinny.hip); returns 1 when it launched.
 int sat_skinny_try(const SatGemm& g, hipStream_t s, int* err);
+int sat_skinny_takes(const SatGemm& g);   // 1 when sat_skinny_try would launch g
 int sat_skinny_splits(int M, int N, int K);
 // weight-stationary 3x3 / stride-1 conv, 64 -> 64 channels, W 56 or 224 (conv3x3ws.hip); returns 1 when it launched.
 int sat_conv3x3_ws_try(const SatGemm& g, hipStream_t s, int* err);   // partial splits the skinny kernel prefers (0 = not eligible)

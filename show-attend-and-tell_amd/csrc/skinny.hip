@@ -471,6 +471,12 @@ int sat_skinny_dual_try(const SatGemm& g1, const SatGemm& g2, hipStream_t st, in
 
 // splits the decoder asks for when the skinny kernel runs its per-step GEMMs: 256-deep K per split
 // (less A per workgroup: every workgroup reads all M rows of its K range), 0 = not eligible
+int sat_skinny_takes(const SatGemm& g) {
+  SkArgs a;
+  int nw;
+  return skinny_shape(g, sat_policy().skinny, &a, &nw) && skinny_ptrs(g) ? 1 : 0;
+}
+
 int sat_skinny_splits(int M, int N, int K) {
   if (sat_policy().skinny == 1 || M > 128 || N % SK_COLS || K % 256 || K < 1024) return 0;
   return K / 256;

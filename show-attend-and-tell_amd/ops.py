@@ -64,6 +64,19 @@ def gemm(A, B, C, *, transA=False, transB=False, alpha=1.0, beta=0.0, bias=None,
     ``policy``: an optional ``sat_amd.Policy`` (per-call kernel selection; None = library defaults).
     ``workspace``: True = this stream's cached split-K workspace (``gemm_workspace``), a uint8 device tensor, or
     None (products with fp32 output and a k-major operand then run unsplit)."""
+    a = _gemm_args(A, B, C, transA, transB, alpha, beta, bias, add1, act, aux, policy)
+    stream = L.stream_of(C)
+    if workspace is True:
+        workspace = (gemm_workspace(C.device, stream)
+                     if policy is not None or _may_split(A, C, bias, aux, act, a.K) else None)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    L.check(L.lib().sat_gemm(ctypes.byref(a), stream), "sat_gemm")
+    return C
+
+
+def _gemm_args(A, B, C, transA=False, transB=False, alpha=1.0, beta=0.0, bias=None, add1=None, act=L.ACT_NONE,
+               aux=None, policy=None):
     L.require_device(A, B, C)
     dt = L.dtype_code(A.dtype)
     if B.dtype != A.dtype:
@@ -90,14 +103,42 @@ def gemm(A, B, C, *, transA=False, transB=False, alpha=1.0, beta=0.0, bias=None,
     if aux is not None:
         a.aux, a.ld_aux, a.aux_dtype = aux.data_ptr(), aux.stride(0), L.dtype_code(aux.dtype)
     a.policy = L.policy_ptr(policy)
-    stream = L.stream_of(C)
-    if workspace is True:
-        workspace = (gemm_workspace(C.device, stream)
-                     if policy is not None or _may_split(A, C, bias, aux, act, K) else None)
-    if workspace is not None:
-        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    L.check(L.lib().sat_gemm(ctypes.byref(a), stream), "sat_gemm")
-    return C
+    return a
+
+
+def gemm_group(products, workspace):
+    """Independent products as one launch (include/sat_hip.h sat_gemm_group).  ``products``: up to 8 dicts of
+    ``gemm``'s arguments (A, B, C and the keywords but ``workspace``), each with its own ``policy``; ``workspace``: a
+    uint8 device tensor of at least ``sat_gemm_group_workspace_bytes()``, which the call may overwrite."""
+    args = (L.SatGemmArgs * len(products))()
+    keep = []
+    for i, p in enumerate(products):
+        a = _gemm_args(**p)
+        keep.append(a)   # the policy pointers stay alive until the call returns
+        ctypes.memmove(ctypes.byref(args[i]), ctypes.byref(a), ctypes.sizeof(a))
+    L.check(L.lib().sat_gemm_group(args, len(products), workspace.data_ptr(),
+                                   workspace.numel() * workspace.element_size(), L.stream_of(products[0]["C"])),
+            "sat_gemm_group")
+
+
+def gemm_group_plan(shapes, slab_bytes, tickets):
+    """The joint planner of a group launch, on the host (include/sat_hip.h sat_gemm_group_plan).  ``shapes``: tuples
+    (M, N, K[, tile_rows[, splits]]); returns one ``SatGemmGroupPlan`` per product."""
+    sh = (L.SatGemmGroupShape * len(shapes))()
+    for i, t in enumerate(shapes):
+        t = tuple(t) + (0, 0)
+        sh[i].M, sh[i].N, sh[i].K, sh[i].tile_rows, sh[i].splits = t[:5]
+    plan = (L.SatGemmGroupPlan * len(shapes))()
+    L.check(L.lib().sat_gemm_group_plan(sh, len(shapes), slab_bytes, tickets, plan), "sat_gemm_group_plan")
+    return plan
+
+
+def gemm_group_block(plan, block):
+    """(product, m-tile, n-tile, split) of a block of a planned group launch; product -1 = no such block."""
+    out = [ctypes.c_int() for _ in range(4)]
+    L.check(L.lib().sat_gemm_group_block(plan, len(plan), block, *[ctypes.byref(o) for o in out]),
+            "sat_gemm_group_block")
+    return tuple(o.value for o in out)
 
 
 def cast_(src, dst):

@@ -7,6 +7,7 @@ gemmsplit.hip, for the fp32-output products with a k-major operand), the 128x128
 = 1) and, with --forms, each split-K form (tile height x split count).
 
     python tools/head_gemms.py [--forms] [--reps 10] [--torch]
+    python tools/head_gemms.py --grouped      # the backward's three sets: one grouped launch against one by one
 """
 import argparse
 import os
@@ -67,13 +68,64 @@ def time_one(A, Bm, C, ta, tb, beta, policy, reps, act=0):
     return st.elapsed_time(en) / reps * 1e3
 
 
+# the decoder backward's three sets of independent products (decoder.hip), by SHAPES name
+GROUPS = [
+    ("head pair", ["dW f_out", "dX f_out"]),
+    ("head four", ["dW f_h", "dW f_z", "dX f_h", "dX f_z"]),
+    ("after the loop", ["dW attention.W", "dW [U; f_beta; W_hh]", "dW W_ih[:, :E]", "dW W_ih[:, E:]", "dX embedding"]),
+]
+EXTRA = [("dW f_h", E, E, R, True, True, torch.float32, 0.0), ("dX f_h", R, E, E, False, True, torch.float32, 0.0)]
+
+
+def grouped(reps):
+    """Each set as one grouped launch (ops.gemm_group) against its products launched one by one, back to back."""
+    shapes = {s[0]: s for s in SHAPES + EXTRA}
+    ws = torch.empty(int(sat_amd._lib.lib().sat_gemm_group_workspace_bytes()), dtype=torch.uint8, device=DEV)
+    plan_ws = int(sat_amd._lib.lib().sat_gemm_workspace_bytes()) - 1024
+    for label, names in GROUPS:
+        prods, dims = [], []
+        for n in names:
+            _, M, N, K, ta, tb, cdt, beta = shapes[n][:8]
+            A, Bm, C = operands(M, N, K, ta, tb, cdt)
+            prods.append(dict(A=A, B=Bm, C=C, transA=ta, transB=tb, beta=beta))
+            dims.append((M, N, K))
+
+        def one_by_one():
+            for p in prods:
+                ops.gemm(p["A"], p["B"], p["C"], transA=p["transA"], transB=p["transB"], beta=p["beta"])
+
+        def as_group():
+            ops.gemm_group(prods, ws)
+        us = []
+        for go in (one_by_one, as_group, one_by_one, as_group):
+            for _ in range(2):
+                go()
+            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            st.record()
+            for _ in range(reps):
+                go()
+            en.record()
+            en.synchronize()
+            us.append(st.elapsed_time(en) / reps * 1e3)
+        plan = ops.gemm_group_plan(dims, plan_ws, 1024)
+        f = sum(2.0 * M * N * K for M, N, K in dims)
+        print(f"{label:16s} one by one {us[0]:7.1f} / {us[2]:7.1f} us   grouped {us[1]:7.1f} / {us[3]:7.1f} us "
+              f"({f / min(us[1], us[3]) / 1e6:6.1f} TF/s)   plan "
+              + " ".join(f"{p.tile_rows}x{p.splits}@{p.first_block}" for p in plan), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grouped", action="store_true",
+                    help="time each set of independent backward products as one grouped launch against its "
+                         "products launched one by one (the grouped time includes its ticket-zeroing launch)")
     ap.add_argument("--forms", action="store_true", help="every split-K form (tile height x splits) of the k-major products")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--torch", action="store_true",
                     help="calibration: torch.matmul (hipBLASLt) of the same bf16 operands, bf16 output")
     a = ap.parse_args()
+    if a.grouped:
+        return grouped(a.reps)
     tot_us = tot_f = tot_tile = tot_lib = 0.0
     for name, M, N, K, ta, tb, cdt, beta, *rest in SHAPES:
         act = rest[0] if rest else 0
