@@ -542,10 +542,15 @@ int sat_caption_loss_backward_ld(int B, int T, int V, int L, int dtype, const vo
  * Decoded uint8 RGB images of any size, packed HWC (image b at pixels + offsets[b], sizes[b] =
  * {H, W}; offsets / sizes are device arrays) -> Resize((OH, OW)) with Pillow's 8-bit BILINEAR
  * resampler (bit-identical bytes) -> ToTensor -> Normalize(mean, std) (host float[3] each) -> the
- * encoder's input layout.  max_h / max_w bound the sizes (downscale <= sat_images_max_downscale()). */
+ * encoder's input layout.  max_h / max_w bound the sizes (downscale <= sat_images_max_downscale()).
+ * One workgroup needs sat_images_lds_bytes(max_h, max_w, OH, OW) bytes of LDS (0 for a non-positive size); a batch
+ * that needs more than sat_images_lds_limit() -- the device's per-workgroup LDS, 160 KiB on gfx950; only outputs
+ * near 512 columns at a 13x or deeper horizontal downscale do -- is SAT_ERR_INVALID before any launch. */
 enum { SAT_IMG_NCHW = 0, SAT_IMG_NHWC = 1, SAT_IMG_S2D16 = 2 };
 size_t sat_images_workspace_bytes(int B, int OH, int OW);
 int sat_images_max_downscale(void);
+size_t sat_images_lds_bytes(int max_h, int max_w, int OH, int OW);
+size_t sat_images_lds_limit(void);
 int sat_images_to_input(const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, int B, int max_h,
                         int max_w, int OH, int OW, const float* mean, const float* std, int layout, int c_pad,
                         int dtype, void* out, void* workspace, size_t workspace_bytes, void* stream);

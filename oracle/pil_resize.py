@@ -7,8 +7,17 @@ The reference resizes with torchvision 0.16's transforms.Resize((224, 224)) on P
 third-party dependency absent from /root/reference; its published 8-bit resampler
 (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc, ImagingResampleHorizontal_8bpc,
 ImagingResampleVertical_8bpc) is restated here with numpy integer arithmetic.  Parity is pinned
-against the Pillow importable in this container and on the GPU box (12.2; the resampler is unchanged
-since 10.1) by tests/test_cpu_images.py: bytes bit-identical for up-, down- and non-scaled sizes.
+against the installed Pillow (12.2) by tests/test_cpu_images.py and tests/test_cpu_image_cases.py:
+bytes bit-identical for up-, down- and non-scaled sizes, 1-pixel axes and 15x downscales included.
+
+Order of the passes.  This oracle and the kernel (csrc/images.hip) always resample horizontally
+first.  Pillow 12.2's Image.resize does so only while h <= 100 w: for an image with h > 100 w whose
+height shrinks it runs the vertical pass first, and because the intermediate image is 8-bit the two
+orders differ by 1 in some bytes (about a fifth of them for 1000x9 -> 224x224).  For such images
+resize_bilinear therefore does NOT equal the installed PIL, while _pass(_pass(img, 0, OH), 1, OW)
+does; tests/test_cpu_image_cases.py pins both, and its case table keeps to h <= 100 w.  Whether the
+reference's pinned Pillow 10.1.0 already had this rule could not be checked: no 10.1.0 was available
+to run, so which order the reference itself used for such images is not known.
 """
 import math
 

@@ -206,6 +206,8 @@ _SIGNATURES = [
                                              c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     ("sat_images_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
     ("sat_images_max_downscale", c_int, []),
+    ("sat_images_lds_bytes", c_size_t, [c_int, c_int, c_int, c_int]),
+    ("sat_images_lds_limit", c_size_t, []),
     ("sat_images_to_input", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                     ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, c_int, c_int, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),

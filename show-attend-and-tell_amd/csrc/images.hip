@@ -3,7 +3,7 @@
 // encoder's first-layer layout, on the GPU.
 //
 // Resize is torchvision 0.16's PIL path, i.e. Pillow's two-pass 8-bit resampler (Pillow 10.1.0
-// pinned by the reference's requirements.txt; unchanged through 12.x), restated from its published
+// pinned by the reference's requirements.txt; checked against 12.2), restated from its published
 // algorithm (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc,
 // ImagingResampleHorizontal_8bpc / Vertical_8bpc, BILINEAR support 1.0):
 //   * per axis and output index: scale = in / out, filterscale = max(scale, 1), support =
@@ -12,21 +12,23 @@
 //     w_x = tri((x + xmin - center + 0.5) / filterscale) normalised to sum 1 in double, then fixed
 //     point int32 = (int)(w * 2^22 +- 0.5);
 //   * horizontal pass first into an 8-bit intermediate, then the vertical pass; each output byte is
-//     clip8((2^21 + sum_x in_x * k_x) >> 22), exactly as Pillow rounds.
+//     clip8((2^21 + sum_x in_x * k_x) >> 22), exactly as Pillow rounds.  (Pillow 12.2 runs the
+//     vertical pass first for images with h > 100 w whose height shrinks; this kernel never does,
+//     and differs from it by 1 in some bytes there: oracle/pil_resize.py.)
 // The coefficient tables are computed on the device in double with contraction off (the same IEEE
 // operations as Pillow's C), so the resized bytes are bit-identical to PIL's.  ToTensor / Normalize
 // are ((float)u / 255 - mean) / std in fp32 with IEEE division, bit-identical to torch's
 // img.float().div(255).sub_(mean).div_(std).
 //
 // Layout: pixels of image b start at offsets[b] (HWC, 3 bytes per pixel); sizes[b] = (H, W).
-// Work split: one workgroup per (image, 8 output rows).  The workgroup resamples the input rows
+// Work split: one workgroup per (image, TY = 16 output rows).  The workgroup resamples the input rows
 // those output rows need horizontally into LDS (at most RCAP rows x OW x 3 bytes; taller spans are
 // processed in sub-chunks), then resamples vertically and writes the requested layout:
 //   SAT_IMG_NCHW  [B, 3, OH, OW] fp32 (the reference's tensor),
 //   SAT_IMG_NHWC  [B, OH, OW, c_pad] (dtype), channels >= 3 zero (VGG19 first conv),
 //   SAT_IMG_S2D16 [B, OH/2, OW/2, 16] (dtype), channel (sy*2 + sx)*3 + c, 12..15 zero (ResNet152
 //   space-to-depth stem; the same layout as sat_nchw_to_s2d).
-// The whole job is one pass over the uint8 input (re-reads only where 8-row tiles' spans overlap)
+// The whole job is one pass over the uint8 input (re-reads only where 16-row tiles' spans overlap)
 // plus one write of the output: HBM-bound byte work, no MFMA.
 #include "sat_common.h"
 #include "sat_internal.h"
@@ -283,12 +285,17 @@ inline int ksize_for(int in, int out) {   // Pillow: (int)ceil(support) * 2 + 1,
   return (int)std::ceil(sc < 1.0 ? 1.0 : sc) * 2 + 1;
 }
 
+// LDS of one workgroup: the row window, the image's horizontal table, the tile's vertical table
+inline size_t lds_bytes_for(int KH, int KV, int OW) {
+  return (size_t)RCAP * OW * 4 + (size_t)OW * (2 + KH) * 4 + (size_t)TY * (2 + KV) * 4;
+}
+
 template <int LAYOUT, typename T>
 void launch_resample(const uint8_t* pix, const int64_t* offsets, const int32_t* sizes, int B, int max_h,
                      int max_w, int OH, int OW, int c_pad, const float* mean, const float* stdv, const int* ws,
                      void* out, hipStream_t s) {
   const int KH = ksize_for(max_w, OW), KV = ksize_for(max_h, OH);
-  const size_t lds = (size_t)RCAP * OW * 4 + (size_t)OW * (2 + KH) * 4 + (size_t)TY * (2 + KV) * 4;
+  const size_t lds = lds_bytes_for(KH, KV, OW);
   const dim3 grid(sat_cdiv(OH, TY), B);
   hipLaunchKernelGGL((resample_kernel<LAYOUT, T>), grid, dim3(256), lds, s, pix, offsets, sizes, OH, OW, c_pad, KH,
                      KV, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], ws, (T*)out);
@@ -302,6 +309,25 @@ extern "C" size_t sat_images_workspace_bytes(int B, int OH, int OW) {
 }
 
 extern "C" int sat_images_max_downscale(void) { return (KMAX - 1) / 2; }
+
+extern "C" size_t sat_images_lds_bytes(int max_h, int max_w, int OH, int OW) {
+  if (max_h <= 0 || max_w <= 0 || OH <= 0 || OW <= 0) return 0;
+  return lds_bytes_for(ksize_for(max_w, OW), ksize_for(max_h, OH), OW);
+}
+
+// LDS one workgroup may ask for: what the device reports, and no less than the 160 KiB of a gfx950 CU that the
+// static LDS of the conv kernels relies on anyway (a runtime that reports a smaller, older figure is not believed)
+extern "C" size_t sat_images_lds_limit(void) {
+  static size_t limit = 0;
+  if (limit == 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess)
+      v = 0;
+    limit = v > 160 * 1024 ? (size_t)v : (size_t)160 * 1024;
+  }
+  return limit;
+}
 
 namespace {
 // A resample / coefficient kernel that hit an unreachable-for-validated-sizes limit sets ws[0] and
@@ -323,6 +349,8 @@ extern "C" int sat_images_to_input(const uint8_t* pixels, const int64_t* offsets
   SAT_REQUIRE(OH > 0 && OW > 0 && OW <= MAX_OW && max_h > 0 && max_w > 0);
   // taps per output index = 2 * ceil(in / out) + 1 at most: keep within KMAX
   SAT_REQUIRE(2 * sat_cdiv(max_h, OH) + 1 <= KMAX && 2 * sat_cdiv(max_w, OW) + 1 <= KMAX);
+  // wide outputs with many horizontal taps outgrow the CU's LDS (OW = 512 with KH >= 29): refuse, launch nothing
+  SAT_REQUIRE(sat_images_lds_bytes(max_h, max_w, OH, OW) <= sat_images_lds_limit());
   SAT_REQUIRE(workspace_bytes >= sat_images_workspace_bytes(B, OH, OW));
   SAT_REQUIRE(dtype == SAT_F32 || dtype == SAT_BF16);
   if (layout == SAT_IMG_NCHW) SAT_REQUIRE(dtype == SAT_F32);

@@ -195,6 +195,10 @@ def images_to_input(packed, layout=L.IMG_NCHW, dtype=torch.float32, c_pad=8, siz
     if packed.max_h > mx * OH or packed.max_w > mx * OW:
         raise ValueError(f"images_to_input: {packed.max_h}x{packed.max_w} exceeds the {mx}x downscale limit "
                          f"to {OH}x{OW}")
+    need, limit = lib.sat_images_lds_bytes(packed.max_h, packed.max_w, OH, OW), lib.sat_images_lds_limit()
+    if need > limit:
+        raise ValueError(f"images_to_input: {packed.max_h}x{packed.max_w} to {OH}x{OW} needs {need} bytes of LDS per "
+                         f"workgroup, above the limit of {limit}")
     dev = packed.pixels.device
     if layout == L.IMG_NCHW:
         if dtype != torch.float32:
