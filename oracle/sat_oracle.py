@@ -130,10 +130,27 @@ def make_dropout_masks(B, steps, E, seed):
 # output-head Linears are column sums of those bf16 values, the others of the fp32 ones).  Everything else (the
 # attention softmax / context, the gates, the LSTM cell, h, c, the loss) stays in the caller's dtype.  Run in fp64,
 # it is the reference the bf16 kernels are measured against with fp32 accumulation noise as the only difference.
+#
+# The beam-search step (csrc/beam.hip beam_step, single-image and batched alike) rounds at the same points, one
+# excepted; in the order a step meets them, ``bf16_mirror(beam=True)`` rounds
+#   * the features themselves: the caller passes bf16 values (the device gets a bf16 tensor); the attention context
+#     and the no-attention mean are fp32 sums of those values;
+#   * the mean features and every weight entering init_h / init_c (h0 is then stored in bf16, c0 in fp32: h is only
+#     ever read as a GEMM operand, so rounding it at each use is the same thing);
+#   * Ws = a W^T + b: bf16 operands, bf16 result (the one rounded GEMM *output* of the beam path);
+#   * the embedding rows (emb_t), h_t, the gated context (gated_t) -- or the mean features without attention -- and
+#     the bf16 W_ih / [U; f_beta; W_hh] they multiply; U h, the f_beta gate, the attention scores / softmax / context
+#     (v is read in fp32), the gates, c and h stay fp32;
+#   * the ado head's operands h_new, ctx_t (the ungated context) with f_h / f_z, then fh + fz + the bf16 embedding
+#     row, summed in fp32 and rounded once to bf16 (comb_t) before f_out;
+#   * NOT the vocabulary logits: beam_step writes them in fp32 (y_dtype = SAT_F32) where the training path stores
+#     bf16 preds, so the candidates the top-k ranks are fp32 sums of an fp32 running score and fp32 logits.
+# ``beam=True`` therefore changes exactly one thing: the head's output (f_out / deep_output) is left unrounded.
 # ----------------------------------------------------------------------------
 
 class _MirrorState:
     on = False
+    round_head = True
 
 
 _MIRROR = _MirrorState()
@@ -142,13 +159,17 @@ _MIRROR = _MirrorState()
 class bf16_mirror:
     """Context manager: the decoder functions of this module round where the HIP bf16 path rounds."""
 
+    def __init__(self, beam=False):
+        """``beam``: round as the beam-search step does -- the vocabulary logits stay unrounded."""
+        self.beam = beam
+
     def __enter__(self):
-        self.prev = _MIRROR.on
-        _MIRROR.on = True
+        self.prev = (_MIRROR.on, _MIRROR.round_head)
+        _MIRROR.on, _MIRROR.round_head = True, not self.beam
         return self
 
     def __exit__(self, *exc):
-        _MIRROR.on = self.prev
+        _MIRROR.on, _MIRROR.round_head = self.prev
         return False
 
 
@@ -193,11 +214,13 @@ def _lin(x, w, b, round_out=False, round_bias_grad=False, mirror=True):
 # Linears whose output the HIP bf16 path stores in bf16, and those whose bias gradient is a column sum of a bf16
 # gradient (the output head's)
 _ROUND_OUT = ("attention.W", "f_out", "deep_output")
+_HEAD_OUT = ("f_out", "deep_output")      # left unrounded inside bf16_mirror(beam=True)
 _ROUND_BIAS_GRAD = ("f_h", "f_z", "f_out", "deep_output")
 
 
 def linear(x, p, name, mirror=True):
-    return _lin(x, p[name + ".weight"], p[name + ".bias"], round_out=any(name.endswith(k) for k in _ROUND_OUT),
+    round_out = any(name.endswith(k) for k in _ROUND_OUT) and (_MIRROR.round_head or name not in _HEAD_OUT)
+    return _lin(x, p[name + ".weight"], p[name + ".bias"], round_out=round_out,
                 round_bias_grad=name in _ROUND_BIAS_GRAD, mirror=mirror)
 
 
@@ -290,12 +313,18 @@ def decoder_forward(p, img_features, captions, *, tf, ado, attention, bert=False
     return preds, alphas, in_tokens
 
 
-def beam_search(p, img_features, beam_size, *, ado, attention, bert=False, max_step=50):
+def beam_search(p, img_features, beam_size, *, ado, attention, bert=False, max_step=50, trace=False, h_hook=None):
     """decoder.py:160-269 (Decoder.caption).  img_features: [beam_size, L, D].
 
     Returns (sentence ids incl. the start token, alpha rows [len][L] incl. the leading ones row,
     score) for the best completed beam; ([0], last alpha rows, -inf) when none completed.  Scores
-    are summed RAW logits (decoder.py:204); ties inside topk go to the lower flat index."""
+    are summed RAW logits (decoder.py:204); ties inside topk go to the lower flat index.
+
+    ``trace=True`` returns a fourth value, a dict for fixture qualification: ``steps`` holds per step the selected
+    candidate ``values`` with their ``parents`` / ``words``, the rows' running ``scores`` going in and the decision
+    ``margin`` (the k-th selected value minus the best rejected one, +inf when nothing is rejected); ``winner_gap`` is the winning completed score minus the best other completed score (+inf
+    with fewer than two completions); ``path_logits`` the raw logits summed into the winner's score.
+    ``h_hook(step, h) -> h`` (fixture qualification only) may replace the hidden state a step's LSTM returns."""
     L = img_features.shape[1]
     V = p["embedding.weight"].shape[0]
     start = SPECIAL_BERT["start"] if bert else SPECIAL_PLAIN["start"]
@@ -304,6 +333,7 @@ def beam_search(p, img_features, beam_size, *, ado, attention, bert=False, max_s
     top_preds = torch.zeros(beam_size, 1)
     alphas = torch.ones(beam_size, 1, L)
     done, done_alpha, done_score = [], [], []
+    steps, path, done_path = [], [[] for _ in range(beam_size)], []
     h, c = init_lstm_state(p, img_features)
     feats = img_features
     step = 1
@@ -318,13 +348,22 @@ def beam_search(p, img_features, beam_size, *, ado, attention, bert=False, max_s
             context = feats.mean(dim=1)
             gated = context
         h, c = lstm_cell(p, torch.cat((emb, gated), dim=1), h, c)
+        if h_hook is not None:
+            h = h_hook(step, h)
         out = advanced_deep_output(p, h, context, emb) if ado else linear(h, p, "deep_output")
         out = top_preds.expand_as(out) + out                             # decoder.py:204
         flat = out[0] if step == 1 else out.reshape(-1)
         # sorted top-k with ties to the lower index: stable sort on -value
-        order = torch.sort(-flat, stable=True).indices[:k]
+        ranked = torch.sort(-flat, stable=True).indices
+        order = ranked[:k]
         top_vals, top_words = flat[order], order
         prev_idx, next_idx = top_words // V, top_words % V                  # decoder.py:210-211
+        if trace:
+            steps.append(dict(values=top_vals.tolist(), parents=prev_idx.tolist(), words=next_idx.tolist(),
+                              scores=top_preds[:, 0].tolist(),
+                              margin=float(top_vals[-1] - flat[ranked[k]]) if len(ranked) > k else float("inf")))
+            path = [path[i] + [float(top_vals[j] - top_preds[i, 0])]
+                    for j, i in enumerate(prev_idx.tolist())]
         sentences = torch.cat((sentences[prev_idx], next_idx.unsqueeze(1)), dim=1)
         alphas = torch.cat((alphas[prev_idx], alpha[prev_idx].unsqueeze(1)), dim=1)
         ends = (1, 0) if bert else (1, 102)                                 # decoder.py:224-229
@@ -334,6 +373,7 @@ def beam_search(p, img_features, beam_size, *, ado, attention, bert=False, max_s
             done.append(sentences[i].tolist())
             done_alpha.append(alphas[i].tolist())
             done_score.append(float(top_vals[i]))
+            done_path.append(path[i] if trace else None)
         if len(incomplete) == 0:
             break
         sentences, alphas = sentences[incomplete], alphas[incomplete]
@@ -341,13 +381,20 @@ def beam_search(p, img_features, beam_size, *, ado, attention, bert=False, max_s
         h, c, feats = h[sel], c[sel], feats[sel]
         top_preds = top_vals[incomplete].unsqueeze(1)
         prev_words = next_idx[incomplete]
+        path = [path[i] for i in incomplete]
         if step > max_step:
             break
         step += 1
     if not done:
-        return [0], alpha.tolist(), float("-inf")
+        res = ([0], alpha.tolist(), float("-inf"))
+        return res + (dict(steps=steps, winner_gap=float("inf"), path_logits=[]),) if trace else res
     best = done_score.index(max(done_score))
-    return done[best], done_alpha[best], done_score[best]
+    res = (done[best], done_alpha[best], done_score[best])
+    if trace:
+        others = done_score[:best] + done_score[best + 1:]
+        gap = done_score[best] - max(others) if others else float("inf")
+        return res + (dict(steps=steps, winner_gap=gap, path_logits=done_path[best]),)
+    return res
 
 
 # ----------------------------------------------------------------------------
