@@ -425,6 +425,31 @@ int sat_decoder_forward_sampled(const SatDecoderDims* d, const SatDecoderLayout*
                                 const uint8_t* dropout_mask, float tf_prob, const float* tf_prob_dev,
                                 const uint8_t* tf_mask, uint8_t* tf_mask_out, void* workspace,
                                 size_t workspace_bytes, void* preds, float* alphas, int32_t* tokens, void* stream);
+/* Sampled feedback (the sample pass of self-critical sequence training, Rennie et al. 2017): sat_decoder_forward
+ * with the decoder drawing its next token from its own distribution.  Step 0 feeds the start token, step t >= 1
+ * feeds sampled[b, t-1], and a token is drawn at every step, the last included:
+ *   sampled[b, t] = argmax_v ( x[b,t,v] + tau * G(seed, b, t, v) )
+ * x = the stored logits of preds (bf16: the rounded values; ado: after the ReLU -- what the greedy argmax reads), the
+ * sum formed in fp32 as one multiply then one add (no contraction), the winner taken in torch.argmax's order (NaN
+ * first, then the value, then the smaller index).  This is the Gumbel-max form of a draw from softmax(x / tau): no
+ * division, tau = 0 is the greedy forward bit for bit, a logit of -inf is never drawn.
+ *   G = -log(-log u), u = (2k + 1) 2^-24, k = the top 23 bits of the 64-bit mix of scheduled sampling's draw taken over
+ *   (seed, b, t, v) under a domain constant of its own: u is exact in fp32 and never 0 or 1, so G is finite.  The seed
+ *   is the dropout's (d->seed ^ f(*d->seed_ptr)); the counter is advanced once per sample-mode forward (training or
+ *   not), so a captured graph draws afresh on every replay.  G depends on (seed, b, t, v) only, not on the loop form.
+ * tau = *temperature_dev when temperature_dev is given (a device scalar read by the kernels), temperature otherwise.
+ * Requires d->tf == 0, temperature >= 0 (NaN refused) and V < 2^20 (SAT_ERR_INVALID otherwise).  captions is
+ * nullable and unread (d->T and d->start_token define the steps).  tokens (nullable, [B, T-1]) receives the fed
+ * tokens, sampled ([B, T-1] int32) the drawn ones.  The workspace is that of d (tf == 0) and sat_decoder_backward runs
+ * on it unchanged: the fed tokens are constants. */
+int sat_decoder_forward_sample(const SatDecoderDims* d, const SatDecoderLayout* lay, const float* params,
+                               const void* params_lp, const void* img_features, const int64_t* captions,
+                               const uint8_t* dropout_mask, float temperature, const float* temperature_dev,
+                               void* workspace, size_t workspace_bytes, void* preds, float* alphas, int32_t* tokens,
+                               int32_t* sampled, void* stream);
+/* diagnostic: out[b, t, v] ([B, T1, V] fp32) = exactly the G values the next sample-mode forward of d will use (the
+ * same device function; only d->seed and d->seed_ptr are read).  Does not advance the counter. */
+int sat_sample_noise(const SatDecoderDims* d, int B, int T1, int V, float* out, void* stream);
 /* phase 1 = output-head gradients only (f_out/f_h/f_z/deep_output), 2 = the rest
  * (needs phase 1 first), 3 = both.  accumulate=0 overwrites the active grads. */
 int sat_decoder_backward(const SatDecoderDims* d, const SatDecoderLayout* lay, const float* params,
@@ -537,6 +562,26 @@ int sat_caption_loss_backward_ld(int B, int T, int V, int L, int dtype, const vo
                                  const int64_t* captions, float alpha_c, void* workspace,
                                  const float* grad_out, void* d_preds, int64_t ld_dpreds,
                                  float* d_alphas, int relu_mask, void* stream);
+/* Token-weighted caption loss (self-critical sequence training's reward-weighted log-likelihood):
+ *   loss = sum_{b, t < T-1} w[b,t] (logsumexp(preds[b,t,:]) - preds[b,t,target[b,t]])
+ *          + alpha_c * mean_{b,l} (1 - sum_t alpha[b,t,l])^2
+ *   d preds[b,t,:] = g * w[b,t] * (softmax(preds[b,t,:]) - onehot(target[b,t]))
+ * targets [B,T-1] int32 and weights [B,T-1] fp32 are device arrays; all T-1 steps are eligible, the weights decide
+ * what is scored.  A row with w == 0 gets an exactly zero gradient row and its logits are not read by the backward.
+ * A target outside [0, V) cannot be refused without a host read: such a row counts as weight 0 (loss, gradient) and
+ * is tallied in out[3]; its logp is 0.  Reductions run in a fixed order (bit-identical reruns).
+ * forward: out[0] = loss, [1] = the weighted CE sum, [2] = att-reg, [3] = # out-of-range targets (out: >= 4 floats);
+ * loss_out (its own 4-byte buffer) = out[0]; logp[b,t] = preds[b,t,target] - logsumexp, fp32 [B,T-1].
+ * backward: the workspace of the forward; ld_dpreds / relu_mask as sat_caption_loss_backward_ld's. */
+size_t sat_caption_loss_weighted_workspace_bytes(int B, int T, int L);
+int sat_caption_loss_weighted_forward(int B, int T, int V, int L, int dtype, const void* preds,
+                                      const float* alphas, const int32_t* targets, const float* weights,
+                                      float alpha_c, void* workspace, float* out, float* loss_out, float* logp,
+                                      void* stream);
+int sat_caption_loss_weighted_backward(int B, int T, int V, int L, int dtype, const void* preds,
+                                       const int32_t* targets, const float* weights, void* workspace,
+                                       const float* grad_out, void* d_preds, int64_t ld_dpreds, float* d_alphas,
+                                       int relu_mask, void* stream);
 
 /* --- streaming image input (train.py:27-32 transform, dataset.py:9-12 decode on the host) ------
  * Decoded uint8 RGB images of any size, packed HWC (image b at pixels + offsets[b], sizes[b] =

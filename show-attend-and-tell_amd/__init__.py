@@ -8,12 +8,14 @@ C ABI in include/sat_hip.h (libsat_hip.so, loaded with ctypes).
 from . import _lib
 from ._lib import SatPolicy as Policy
 from .attention import Attention
+from .cider import CiderD
 from .data import PackedImages, collate_packed
 from .decoder import Decoder
 from .encoder import Encoder
 from .feature_cache import FeatureCache
-from .loss import caption_loss, special_ids, StepMetrics, RunningMeters
+from .loss import (caption_loss, special_ids, StepMetrics, RunningMeters, weighted_caption_loss,
+                   scst_weights)
 from .optim import Adam
 
 __all__ = ["Attention", "Decoder", "Encoder", "caption_loss", "special_ids", "StepMetrics", "RunningMeters", "Adam",
-           "PackedImages", "collate_packed", "FeatureCache"]
+           "PackedImages", "collate_packed", "FeatureCache", "weighted_caption_loss", "scst_weights", "CiderD"]

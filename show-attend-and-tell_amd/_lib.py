@@ -170,6 +170,10 @@ _SIGNATURES = [
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
+    ("sat_decoder_forward_sample", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout),
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                           c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("sat_sample_noise", c_int, [ctypes.POINTER(SatDecoderDims), c_int, c_int, c_int, c_void_p, c_void_p]),
     ("sat_decoder_backward", c_int, [ctypes.POINTER(SatDecoderDims), ctypes.POINTER(SatDecoderLayout), c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -204,6 +208,12 @@ _SIGNATURES = [
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("sat_caption_loss_backward_ld", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                              c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    ("sat_caption_loss_weighted_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
+    ("sat_caption_loss_weighted_forward", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    ("sat_caption_loss_weighted_backward", c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     ("sat_images_workspace_bytes", c_size_t, [c_int, c_int, c_int]),
     ("sat_images_max_downscale", c_int, []),
     ("sat_images_lds_bytes", c_size_t, [c_int, c_int, c_int, c_int]),

@@ -316,6 +316,47 @@ struct Sampled {
   float p; const float* p_dev;
   const uint8_t* mask; uint8_t* mask_out;
 };
+// the per-call inputs of the sample-mode forward (sat_decoder_forward_sample; nullptr: the other entries' paths)
+struct Draw {
+  float tau; const float* tau_dev;
+  int32_t* sampled;   // [B, T-1]: the token drawn at every step
+};
+inline SatSampleArgs sample_args(const SatDecoderDims& d, const Draw& dr, int t) {
+  return SatSampleArgs{d.seed, (const uint64_t*)d.seed_ptr, dr.tau, dr.tau_dev, t};
+}
+// sample mode, after the fused loop: sampled[b, t] = the token fed at t + 1 (t < T1 - 1; the LSTM kernel's fold of step
+// t's partials) and, at the last step, the reduction of its partials here (sat_argmax_better's order, the fold's clamp)
+__global__ __launch_bounds__(64) void sampled_finish_kernel(const int32_t* __restrict__ tok, const float* __restrict__ pval,
+                                                            const int32_t* __restrict__ pidx, int ncb, int B, int T1,
+                                                            int V, int32_t* __restrict__ sampled) {
+  const int b = blockIdx.x;
+  for (int t = threadIdx.x; t < T1 - 1; t += 64) sampled[(long)b * T1 + t] = tok[(long)b * T1 + t + 1];
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = threadIdx.x; c < ncb; c += 64) {
+    const float x = pval[(long)c * B + b];
+    const int xi = pidx[(long)c * B + b];
+    if (sat_argmax_better(x, xi, best, bi)) { best = x; bi = xi; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (sat_argmax_better(ov, oi, best, bi)) { best = ov; bi = oi; }
+  }
+  if (threadIdx.x == 0) sampled[(long)b * T1 + T1 - 1] = (bi < 0 || bi >= V) ? 0 : bi;
+}
+// sat_sample_noise: out[b, t, v] = G(seed ^ f(*seed_ptr), b, t, v), the device function of the sample-form kernels
+__global__ __launch_bounds__(256) void sample_noise_kernel(uint64_t seed, const uint64_t* __restrict__ seed_ptr, int B,
+                                                           int T1, int V, float* __restrict__ out) {
+  if (seed_ptr) seed ^= *seed_ptr * 0xD1B54A32D192ED03ULL;
+  const long n = (long)B * T1 * V;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int v = (int)(i % V);
+    const long r = i / V;
+    out[i] = sat_sample_gumbel(seed, (int)(r / T1), (int)(r % T1), v);
+  }
+}
 // the pre-resolved words [B, T-1] live in a backward-only region of the workspace (free during the forward)
 inline int32_t* tok_pre(const WS& w) { return (int32_t*)w.demb; }
 
@@ -636,8 +677,10 @@ struct StepTimer {
 // full-row argmax.  The embedding half of the gate GEMM depends only on the fed token, so it is one GEMM over the
 // vocabulary per forward (xt = emb W_ih[:, :E]^T + b_ih, once per weight version) and a row gather per step.
 // sm (scheduled sampling, nullable): the token fold selects per row between the caption's token and the argmax
+// dr (sample mode, nullable): the head's sample instance writes the partials of x + tau G, which the unchanged fold
+// reduces; the last step's partials are reduced by one small launch after the loop
 int greedy_loop(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, void* preds, const uint8_t* mask_in,
-                int32_t* tokens, hipStream_t s, const Sampled* sm = nullptr) {
+                int32_t* tokens, hipStream_t s, const Sampled* sm = nullptr, const Draw* dr = nullptr) {
   const SatDecoderDims& d = c.d;
   const SatDecoderLayout& lay = c.lay;
   const int B = d.B, D = d.D, E = d.E, V = d.V, T1 = d.T - 1;
@@ -714,9 +757,15 @@ int greedy_loop(const Ctx& c, const WS& w, const Splits& sp, const StepIO& io, v
     }
     ho.preds = (bf16*)c.at(preds, (long)t * V); ho.preds_ld = c.T1 * V;
     ho.pval = w.am_val; ho.pidx = w.am_idx;
+    if (dr) { ho.sample = 1; ho.smp = sample_args(d, *dr, t); }
     SAT_CHECK((hipError_t)sat_greedy_head_out(ho, s));
   }
-  if (d.training && d.seed_ptr) SAT_CHECK((hipError_t)sat_bump_seed(d.seed_ptr, s));
+  if (dr) {
+    hipLaunchKernelGGL(sampled_finish_kernel, dim3(B), dim3(64), 0, s, (const int32_t*)w.tok, (const float*)w.am_val,
+                       (const int32_t*)w.am_idx, sat_greedy_head_blocks(B, V, E), B, T1, V, dr->sampled);
+    SAT_LAUNCH_CHECK();
+  }
+  if ((d.training || dr) && d.seed_ptr) SAT_CHECK((hipError_t)sat_bump_seed(d.seed_ptr, s));
   if (tokens) SAT_CHECK(hipMemcpyAsync(tokens, w.tok, c.R * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -828,13 +877,14 @@ extern "C" int sat_decoder_instance(const SatDecoderDims* dp, const SatDecoderLa
 
 namespace {
 // sat_decoder_forward (sm == nullptr: every launch as before) and sat_decoder_forward_sampled (sm: d.tf == 0, the
-// greedy loops with the select form of the kernel that produces the fed token)
+// greedy loops with the select form of the kernel that produces the fed token) and sat_decoder_forward_sample (dr:
+// d.tf == 0, the greedy loops with the sample form of that kernel, resolved at every step, the last included)
 int decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params, const void* params_lp,
                     const void* img_features, const int64_t* captions, const uint8_t* dropout_mask, void* workspace,
                     size_t workspace_bytes, void* preds, float* alphas, int32_t* tokens, void* stream,
-                    const Sampled* sm) {
+                    const Sampled* sm, const Draw* dr = nullptr) {
   SAT_CHECK((hipError_t)check_dims(dp));
-  SAT_REQUIRE(lay && params && img_features && captions && workspace && preds && alphas);
+  SAT_REQUIRE(lay && params && img_features && (captions || dr) && workspace && preds && alphas);
   SAT_REQUIRE(dp->dtype == SAT_F32 || params_lp);
   SAT_REQUIRE(!(dp->training && dp->has_dropout_mask) || dropout_mask);
   SatPolicyScope scope(dp->policy);
@@ -899,7 +949,7 @@ int decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const
     SAT_CHECK((hipError_t)linear(c, (int)c.R, 4 * E, E, w.emb_t, E, c.W(lay->wih), E + D, c.F(lay->bih), w.xg, 4 * E,
                                  SAT_F32, SAT_ACT_NONE, s));
 
-  if (greedy_fused(d)) return greedy_loop(c, w, sp, io, preds, dropout_mask, tokens, s, sm);
+  if (greedy_fused(d)) return greedy_loop(c, w, sp, io, preds, dropout_mask, tokens, s, sm, dr);
 
   for (int t = 0; t < T1; ++t) {
     if (!d.tf)
@@ -923,7 +973,14 @@ int decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const
     }
     if (!d.tf) {
       SAT_CHECK((hipError_t)head_forward(c, w, B, t, true, preds, dropout_mask, s));
-      if (t + 1 < T1 && sm)   // scheduled sampling: the caption's token where the row's keep bit is set
+      if (dr) {   // sample mode: a draw at every step, fed to the next one where there is one
+        const bool more = t + 1 < T1;
+        SAT_CHECK((hipError_t)sat_argmax_rows_sample(c.at(preds, (long)t * d.V), d.dtype, (long)T1 * d.V, B, d.V,
+                                                     more ? w.tok + t + 1 : nullptr, T1, dr->sampled + t, T1,
+                                                     c.F(lay->embedding), E,
+                                                     more ? c.at(w.emb_t, (long)(t + 1) * E) : nullptr, (long)T1 * E,
+                                                     sample_args(d, *dr, t), s));
+      } else if (t + 1 < T1 && sm)   // scheduled sampling: the caption's token where the row's keep bit is set
         SAT_CHECK((hipError_t)sat_argmax_rows_select(c.at(preds, (long)t * d.V), d.dtype, (long)T1 * d.V, B, d.V,
                                                      w.tok + t + 1, T1, c.F(lay->embedding), E,
                                                      c.at(w.emb_t, (long)(t + 1) * E), (long)T1 * E,
@@ -935,7 +992,7 @@ int decoder_forward(const SatDecoderDims* dp, const SatDecoderLayout* lay, const
     }
   }
   if (d.tf) SAT_CHECK((hipError_t)head_forward(c, w, (int)c.R, 0, false, preds, dropout_mask, s));
-  if (d.training && d.seed_ptr) SAT_CHECK((hipError_t)sat_bump_seed(d.seed_ptr, s));
+  if ((d.training || dr) && d.seed_ptr) SAT_CHECK((hipError_t)sat_bump_seed(d.seed_ptr, s));
   if (tokens) SAT_CHECK(hipMemcpyAsync(tokens, w.tok, c.R * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -962,6 +1019,30 @@ extern "C" int sat_decoder_forward_sampled(const SatDecoderDims* dp, const SatDe
   const Sampled sm{captions, tf_prob, tf_prob_dev, tf_mask, tf_mask_out};
   return decoder_forward(dp, lay, params, params_lp, img_features, captions, dropout_mask, workspace, workspace_bytes,
                          preds, alphas, tokens, stream, &sm);
+}
+
+// Sampled feedback (self-critical sequence training's sample pass): every step feeds the token drawn at the previous
+// one from the decoder's own distribution: see sat_hip.h
+extern "C" int sat_decoder_forward_sample(const SatDecoderDims* dp, const SatDecoderLayout* lay, const float* params,
+                                          const void* params_lp, const void* img_features, const int64_t* captions,
+                                          const uint8_t* dropout_mask, float temperature, const float* temperature_dev,
+                                          void* workspace, size_t workspace_bytes, void* preds, float* alphas,
+                                          int32_t* tokens, int32_t* sampled, void* stream) {
+  SAT_REQUIRE(dp && dp->tf == 0 && sampled);
+  SAT_REQUIRE(temperature >= 0.f);   // also refuses NaN
+  SAT_REQUIRE(dp->V < (1 << 20) && dp->T <= (1 << 20));   // the noise word's index packing
+  const Draw dr{temperature, temperature_dev, sampled};
+  return decoder_forward(dp, lay, params, params_lp, img_features, captions, dropout_mask, workspace, workspace_bytes,
+                         preds, alphas, tokens, stream, nullptr, &dr);
+}
+
+extern "C" int sat_sample_noise(const SatDecoderDims* d, int B, int T1, int V, float* out, void* stream) {
+  SAT_REQUIRE(d && out && B > 0 && T1 > 0 && V > 0 && V < (1 << 20) && T1 < (1 << 20));
+  const long n = (long)B * T1 * V;
+  const int g = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  hipLaunchKernelGGL(sample_noise_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, d->seed,
+                     (const uint64_t*)d->seed_ptr, B, T1, V, out);
+  return (int)hipGetLastError();
 }
 
 namespace {

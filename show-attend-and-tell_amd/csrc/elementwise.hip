@@ -610,16 +610,28 @@ __device__ __forceinline__ void am_wave_reduce(float& v, int& i) {
 // SEL: scheduled sampling's select form (sat_argmax_rows_select): the row's pre-resolved word (decoder.hip
 // tf_prefill_kernel) is requested before the row scan, and the fed token is that word where it is >= 0, the argmax
 // elsewhere
+// SMP: the sample form (sat_argmax_rows_sample): element v of row b competes as x + tau * G(seed, b, t, v)
+// (sat_internal.h), the noise computed inside the row scan; out2 receives the drawn token besides out
 constexpr int AM_NV = 8;
-template <typename T, bool VECP, bool SEL = false>
+template <typename T, bool VECP, bool SEL = false, bool SMP = false>
 __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ X, long ld, int V, int32_t* __restrict__ out,
                                                      long out_stride, const float* __restrict__ emb, int E,
                                                      T* __restrict__ emb_out, long emb_ld,
-                                                     const int32_t* __restrict__ pre, long pre_stride) {
+                                                     const int32_t* __restrict__ pre, long pre_stride,
+                                                     SatSampleArgs sa = SatSampleArgs{},
+                                                     int32_t* __restrict__ out2 = nullptr, long out2_stride = 0) {
   constexpr int VEC = 16 / sizeof(T);
   const int b = blockIdx.x, tid = threadIdx.x;
   int pre_tok = -1;
   if (SEL) pre_tok = pre[(long)b * pre_stride];
+  uint64_t smp_seed = 0;
+  float tau = 0.f;
+  if constexpr (SMP) { smp_seed = sat_sample_seed(sa); tau = sat_sample_tau(sa); }
+  // the value element v competes with
+  auto val = [&](float x, int v) {
+    if constexpr (SMP) return sat_sample_value(x, tau, sat_sample_gumbel(smp_seed, b, sa.t, v));
+    else return x;
+  };
   const T* row = X + (long)b * ld;
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -639,19 +651,19 @@ __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ X, lo
           const T* h = (const T*)&u[j];
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
-            const float x = (float)h[e];
+            const float x = val((float)h[e], vi * VEC + e);
             if (am_better(x, vi * VEC + e, best, bi)) { best = x; bi = vi * VEC + e; }
           }
         }
       }
     }
     for (int v = nvec * VEC + tid; v < V; v += 256) {
-      const float x = (float)row[v];
+      const float x = val((float)row[v], v);
       if (am_better(x, v, best, bi)) { best = x; bi = v; }
     }
   } else {
     for (int v = tid; v < V; v += 256) {
-      const float x = (float)row[v];
+      const float x = val((float)row[v], v);
       if (am_better(x, v, best, bi)) { best = x; bi = v; }
     }
   }
@@ -668,6 +680,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ X, lo
   if (id < 0 || id >= V) id = 0;
   if (SEL) id = (pre_tok >= 0 && pre_tok < V) ? pre_tok : id;
   if (tid == 0 && out) out[(long)b * out_stride] = id;
+  if (SMP && tid == 0 && out2) out2[(long)b * out2_stride] = id;
   if (emb_out) {
     const float* src = emb + (long)id * E;
     for (int e = tid; e < E; e += 256) emb_out[(long)b * emb_ld + e] = (T)src[e];
@@ -893,6 +906,22 @@ int sat_argmax_rows_select(const void* X, int dtype, long ld, int B, int V, int3
   } else {
     if (vec) hipLaunchKernelGGL((argmax_kernel<float, true, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, pre, pre_stride);
     else hipLaunchKernelGGL((argmax_kernel<float, false, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, pre, pre_stride);
+  }
+  return (int)hipGetLastError();
+}
+
+int sat_argmax_rows_sample(const void* X, int dtype, long ld, int B, int V, int32_t* out, long out_stride,
+                           int32_t* out2, long out2_stride, const float* emb, int E, void* emb_out, long emb_ld,
+                           const SatSampleArgs& sa, hipStream_t s) {
+  if (V >= (1 << 20) || sa.t < 0 || sa.t >= (1 << 20)) return (int)hipErrorInvalidValue;   // the noise word's packing
+  const int esz = dtype == SAT_BF16 ? 2 : 4;
+  const bool vec = ((uintptr_t)X & 15) == 0 && (ld * esz) % 16 == 0;
+  if (dtype == SAT_BF16) {
+    if (vec) hipLaunchKernelGGL((argmax_kernel<bf16, true, false, true>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld, nullptr, 0, sa, out2, out2_stride);
+    else hipLaunchKernelGGL((argmax_kernel<bf16, false, false, true>), dim3(B), dim3(256), 0, s, (const bf16*)X, ld, V, out, out_stride, emb, E, (bf16*)emb_out, emb_ld, nullptr, 0, sa, out2, out2_stride);
+  } else {
+    if (vec) hipLaunchKernelGGL((argmax_kernel<float, true, false, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, nullptr, 0, sa, out2, out2_stride);
+    else hipLaunchKernelGGL((argmax_kernel<float, false, false, true>), dim3(B), dim3(256), 0, s, (const float*)X, ld, V, out, out_stride, emb, E, (float*)emb_out, emb_ld, nullptr, 0, sa, out2, out2_stride);
   }
   return (int)hipGetLastError();
 }

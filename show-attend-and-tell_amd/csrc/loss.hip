@@ -59,17 +59,47 @@ __device__ __forceinline__ void write_row_stats(float* stats, int r, int T1, int
   st[4] = nonpad ? 1.f : 0.f;
 }
 
+// The token-weighted form (sat_caption_loss_weighted_*): row r = (b, t) scores target[r] with weight w[r] over all
+// T-1 steps.  A target outside [0, V) cannot be refused without a host read, so such a row counts as weight 0 and is
+// tallied (out[3]).
+struct WArgs {
+  const int32_t* target;   // [B, T-1]
+  const float* w;          // [B, T-1]
+  float* logp;             // [B, T-1] out (forward): x_target - lse
+};
+// the weighted row's statistics: log-sum-exp, w (lse - x_target), the out-of-range flag; logp
+__device__ __forceinline__ void write_wrow_stats(float* stats, const WArgs& wa, int r, int V, int tgt, float lse,
+                                                 float xt) {
+  const bool valid = tgt >= 0 && tgt < V;
+  const float w = valid ? wa.w[r] : 0.f;
+  float* st = stats + (long)r * kStat;
+  st[0] = lse;
+  st[1] = w != 0.f ? w * (lse - xt) : 0.f;
+  st[2] = valid ? 0.f : 1.f;
+  st[3] = 0.f;
+  st[4] = 0.f;
+  wa.logp[r] = valid ? xt - lse : 0.f;
+}
+
 // PAIRS: the bf16 pair path for even V % 8 != 0 (its own instantiation: its 64-register row would lower the
 // occupancy of the others)
-template <typename TT, bool PAIRS = false>
+// WT: the token-weighted form (the target and the row's term from WArgs; an instance of its own)
+template <typename TT, bool PAIRS = false, bool WT = false>
 __global__ __launch_bounds__(256) void loss_rows_kernel(const TT* __restrict__ preds, const int64_t* __restrict__ caps,
-                                                        int B, int T, int V, int pad_id, float* __restrict__ stats) {
+                                                        int B, int T, int V, int pad_id, float* __restrict__ stats,
+                                                        WArgs wa = WArgs{}) {
   __shared__ float red_m[4], red_s[4], red_c[4];
   const int r = blockIdx.x;
   const int T1 = T - 1;
   const int b = r / T1, t = r - b * T1;
   const TT* x = preds + (long)r * V;
-  const int tgt = (int)caps[(long)b * T + t + 1];
+  int tgt;
+  if constexpr (WT) tgt = wa.target[r];
+  else tgt = (int)caps[(long)b * T + t + 1];
+  auto write_stats = [&](float lse, float xt_, float C) {
+    if constexpr (WT) write_wrow_stats(stats, wa, r, V, tgt, lse, xt_);
+    else write_row_stats(stats, r, T1, t, lse, xt_, C, tgt != pad_id);
+  };
   const float xt = (tgt >= 0 && tgt < V) ? (float)x[tgt] : 0.f;
   float m = -INFINITY, se = 0.f, cnt = 0.f;
   constexpr int VEC = 16 / sizeof(TT);
@@ -117,7 +147,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const TT* __restrict__ p
     if (threadIdx.x == 0) {
       const float S = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
       const float C = (red_c[0] + red_c[1]) + (red_c[2] + red_c[3]);
-      write_row_stats(stats, r, T1, t, M + logf(S), xt, C, tgt != pad_id);
+      write_stats(M + logf(S), xt, C);
     }
     return;
   }
@@ -167,7 +197,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const TT* __restrict__ p
       if (threadIdx.x == 0) {
         const float S = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
         const float C = (red_c[0] + red_c[1]) + (red_c[2] + red_c[3]);
-        write_row_stats(stats, r, T1, t, M + logf(S), xt, C, tgt != pad_id);
+        write_stats(M + logf(S), xt, C);
       }
       return;
     }
@@ -224,7 +254,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const TT* __restrict__ p
       M = nm;
       C += red_c[i];
     }
-    write_row_stats(stats, r, T1, t, M + logf(S), xt, C, tgt != pad_id);
+    write_stats(M + logf(S), xt, C);
   }
 }
 
@@ -284,26 +314,65 @@ __global__ __launch_bounds__(1024) void loss_reduce_kernel(const float* __restri
   }
 }
 
+// the weighted loss's fold: rows in loss_reduce_kernel's fixed order.  out[0] = loss, [1] = the weighted CE sum,
+// [2] = the attention regulariser, [3] = rows whose target was out of range (counted as weight 0)
+__global__ __launch_bounds__(1024) void wloss_reduce_kernel(const float* __restrict__ stats, const float* __restrict__ part,
+                                                            int nparts, int R, int BL, float alpha_c,
+                                                            float* __restrict__ out, float* __restrict__ loss_out) {
+  __shared__ float red[16];
+  float ce = 0.f, bad = 0.f;
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    const float* st = stats + (long)r * kStat;
+    ce += st[1]; bad += st[2];
+  }
+  ce = block_sum(ce, red);
+  bad = block_sum(bad, red);
+  float reg = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) reg += part[i];
+  reg = block_sum(reg, red);
+  if (threadIdx.x == 0) {
+    const float regm = alpha_c * (reg * (1.0f / (float)BL));
+    out[0] = ce + regm;
+    loss_out[0] = ce + regm;
+    out[1] = ce;
+    out[2] = regm;
+    out[3] = bad;
+  }
+}
+
 // dL/dlogit = g * (softmax - onehot) / (B*(T-2)) for scored rows, 0 for the unscored last step.
 // MASK: the logits are a ReLU's output (decoder.py:117-125 advanced deep output), and the
 // gradient leaves through that ReLU: zero where the logit is not positive (fused here so the
 // decoder skips its own mask pass over the [B*(T-1), V] gradient).  16-byte vectors when
 // V % (16 / sizeof(T)) == 0.
-template <typename TT, bool MASK>
+// WT: the token-weighted form (an instance of its own): dL/dlogit = g * w[r] * (softmax - onehot(target[r])); a row of
+// weight 0 (or an out-of-range target) is written as zeros without its logits being read
+template <typename TT, bool MASK, bool WT = false>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const TT* __restrict__ preds, const int64_t* __restrict__ caps,
                                                        int B, int T, int V, int L, const float* __restrict__ stats,
                                                        const float* __restrict__ dreg, const float* __restrict__ grad_out,
-                                                       TT* __restrict__ dpreds, long ldo, float* __restrict__ dalphas) {
+                                                       TT* __restrict__ dpreds, long ldo, float* __restrict__ dalphas,
+                                                       WArgs wa = WArgs{}) {
   const int r = blockIdx.x;
   const int T1 = T - 1;
   const int b = r / T1, t = r - b * T1;
   const float g = grad_out ? grad_out[0] : 1.f;
   const TT* x = preds + (long)r * V;
   TT* dx = dpreds + (long)r * ldo;
-  const bool scored = t < T1 - 1;
-  const int tgt = scored ? (int)caps[(long)b * T + t + 1] : -1;
+  bool scored;
+  int tgt;
+  float scale;
+  if constexpr (WT) {
+    tgt = wa.target[r];
+    const float w = (tgt >= 0 && tgt < V) ? wa.w[r] : 0.f;
+    scored = w != 0.f;
+    scale = g * w;
+  } else {
+    scored = t < T1 - 1;
+    tgt = scored ? (int)caps[(long)b * T + t + 1] : -1;
+    scale = scored ? g / (float)(B * (T1 - 1)) : 0.f;
+  }
   const float lse = scored ? stats[(long)r * kStat] : 0.f;
-  const float scale = scored ? g / (float)(B * (T1 - 1)) : 0.f;
   auto grad = [&](float xv, int v) {
     float p = scored ? expf(xv - lse) : 0.f;
     if (v == tgt) p -= 1.f;
@@ -312,7 +381,12 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const TT* __restrict__ pr
     return d;
   };
   constexpr int VEC = 16 / sizeof(TT);
-  if (V % VEC == 0 && ldo % VEC == 0) {
+  if (WT && !scored) {   // an exactly zero row (pad columns included), the logits unread
+    if (ldo % VEC == 0 && ((uintptr_t)dpreds & 15) == 0)
+      for (long c = threadIdx.x; c < ldo / VEC; c += blockDim.x) *(uint4*)(dx + c * VEC) = make_uint4(0u, 0u, 0u, 0u);
+    else
+      for (long v = threadIdx.x; v < ldo; v += blockDim.x) dx[v] = (TT)0.f;
+  } else if (V % VEC == 0 && ldo % VEC == 0) {
     const __amdgpu_buffer_rsrc_t rdx = sat_out_rsrc(dx, (long)sizeof(TT) * V);   // this row: offsets < 2 GiB
     constexpr int LU = 4;   // vectors per thread in flight
     const int NV = V / VEC;
@@ -466,4 +540,70 @@ extern "C" int sat_caption_loss_backward_ld(int B, int T, int V, int L, int dtyp
   (void)alpha_c;
   return loss_backward(B, T, V, L, dtype, preds, captions, workspace, grad_out, d_preds, (long)ld_dpreds, d_alphas,
                        relu_mask != 0, (hipStream_t)stream);
+}
+
+// ---- the token-weighted caption loss (self-critical sequence training's reward-weighted log-likelihood) ----
+// stats [R, kStat] | dreg [B, L] | reg partials
+extern "C" size_t sat_caption_loss_weighted_workspace_bytes(int B, int T, int L) {
+  return sat_caption_loss_workspace_bytes(B, T, L);
+}
+
+extern "C" int sat_caption_loss_weighted_forward(int B, int T, int V, int L, int dtype, const void* preds,
+                                                 const float* alphas, const int32_t* targets, const float* weights,
+                                                 float alpha_c, void* workspace, float* out, float* loss_out,
+                                                 float* logp, void* stream) {
+  SAT_REQUIRE(preds && alphas && targets && weights && workspace && out && loss_out && logp);
+  SAT_REQUIRE(B > 0 && T >= 2 && V > 0 && L > 0 && (dtype == SAT_F32 || dtype == SAT_BF16));
+  hipStream_t s = (hipStream_t)stream;
+  const int R = B * (T - 1);
+  float* stats = (float*)workspace;
+  float* dreg = stats + (size_t)R * kStat;
+  const WArgs wa{targets, weights, logp};
+  if (dtype == SAT_BF16 && V % 8 != 0 && V % 2 == 0 && V / 2 <= 64 * 256)
+    hipLaunchKernelGGL((loss_rows_kernel<bf16, true, true>), dim3(R), dim3(256), 0, s, (const bf16*)preds, nullptr, B, T,
+                       V, 0, stats, wa);
+  else if (dtype == SAT_BF16)
+    hipLaunchKernelGGL((loss_rows_kernel<bf16, false, true>), dim3(R), dim3(256), 0, s, (const bf16*)preds, nullptr, B,
+                       T, V, 0, stats, wa);
+  else
+    hipLaunchKernelGGL((loss_rows_kernel<float, false, true>), dim3(R), dim3(256), 0, s, (const float*)preds, nullptr, B,
+                       T, V, 0, stats, wa);
+  SAT_LAUNCH_CHECK();
+  float* part = dreg + (size_t)B * L;
+  const int nparts = sat_cdiv((long)B * L, 256);
+  hipLaunchKernelGGL(loss_reg_kernel, dim3(nparts), dim3(256), 0, s, alphas, B, T - 1, L, alpha_c, dreg, part);
+  SAT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wloss_reduce_kernel, dim3(1), dim3(1024), 0, s, (const float*)stats, (const float*)part, nparts, R,
+                     B * L, alpha_c, out, loss_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sat_caption_loss_weighted_backward(int B, int T, int V, int L, int dtype, const void* preds,
+                                                  const int32_t* targets, const float* weights, void* workspace,
+                                                  const float* grad_out, void* d_preds, int64_t ld_dpreds,
+                                                  float* d_alphas, int relu_mask, void* stream) {
+  SAT_REQUIRE(preds && targets && weights && workspace && d_preds && d_alphas && B > 0 && T >= 2 && V > 0 && L > 0);
+  SAT_REQUIRE(ld_dpreds >= V && (dtype == SAT_F32 || dtype == SAT_BF16));
+  hipStream_t s = (hipStream_t)stream;
+  const int R = B * (T - 1);
+  const long ldo = (long)ld_dpreds;
+  const float* stats = (const float*)workspace;
+  const float* dreg = stats + (size_t)R * kStat;
+  const WArgs wa{targets, weights, nullptr};
+  if (dtype == SAT_BF16) {
+    if (relu_mask)
+      hipLaunchKernelGGL((loss_bwd_kernel<bf16, true, true>), dim3(R), dim3(256), 0, s, (const bf16*)preds, nullptr, B,
+                         T, V, L, stats, dreg, grad_out, (bf16*)d_preds, ldo, d_alphas, wa);
+    else
+      hipLaunchKernelGGL((loss_bwd_kernel<bf16, false, true>), dim3(R), dim3(256), 0, s, (const bf16*)preds, nullptr, B,
+                         T, V, L, stats, dreg, grad_out, (bf16*)d_preds, ldo, d_alphas, wa);
+  } else {
+    if (relu_mask)
+      hipLaunchKernelGGL((loss_bwd_kernel<float, true, true>), dim3(R), dim3(256), 0, s, (const float*)preds, nullptr,
+                         B, T, V, L, stats, dreg, grad_out, (float*)d_preds, ldo, d_alphas, wa);
+    else
+      hipLaunchKernelGGL((loss_bwd_kernel<float, false, true>), dim3(R), dim3(256), 0, s, (const float*)preds, nullptr,
+                         B, T, V, L, stats, dreg, grad_out, (float*)d_preds, ldo, d_alphas, wa);
+  }
+  return (int)hipGetLastError();
 }

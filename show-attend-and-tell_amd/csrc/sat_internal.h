@@ -64,6 +64,41 @@ int sat_argmax_rows_select(const void* X, int dtype, long ld, int B, int V, int3
                            const float* emb, int E, void* emb_out, long emb_ld, const int32_t* pre, long pre_stride,
                            hipStream_t s);
 
+// ---- sampled feedback (sat_decoder_forward_sample): the token drawn at step t of row b is
+//   argmax_v ( x[b,t,v] + tau * G(seed, b, t, v) )      (Gumbel-max: a draw from softmax(x / tau), no division,
+// tau = 0 the greedy argmax, a -inf logit never drawn), the sum an explicit fp32 multiply then add (no contraction),
+// reduced in sat_argmax_better's order.  G = -log(-log u), u = (2k + 1) 2^-24 with k the top 23 bits of
+// sat_tf_uniform's mix over (seed, b, t, v) under a domain constant of its own: exact in fp32, never 0 or 1, so G is
+// finite; a function of (seed, b, t, v) only, so both loop forms and every workgroup of a row draw the same noise.
+// v < 2^20, t < 2^20: the three indices occupy disjoint bit ranges of the mixed word.
+constexpr uint64_t kSatSampleDomain = 0x3C6EF372FE94F82BULL;
+__device__ __forceinline__ float sat_sample_gumbel(uint64_t seed, int b, int t, int v) {
+  uint64_t x = (seed ^ kSatSampleDomain) * 0x9E3779B97F4A7C15ULL +
+               (((uint64_t)b << 40) ^ ((uint64_t)t << 20) ^ (uint64_t)v);
+  x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
+  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
+  x ^= x >> 33;
+  const float u = (float)(2u * (uint32_t)(x >> 41) + 1u) * (1.0f / 16777216.0f);
+  return -logf(-logf(u));
+}
+// the per-launch inputs of a sample-form kernel: the dropout's seed pair (seed ^ f(*seed_ptr), decoder.hip), the
+// temperature by value or through a device scalar, and the step
+struct SatSampleArgs {
+  uint64_t seed; const uint64_t* seed_ptr;
+  float tau; const float* tau_dev;
+  int t;
+};
+__device__ __forceinline__ uint64_t sat_sample_seed(const SatSampleArgs& sa) {
+  return sa.seed_ptr ? sa.seed ^ (*sa.seed_ptr * 0xD1B54A32D192ED03ULL) : sa.seed;
+}
+__device__ __forceinline__ float sat_sample_tau(const SatSampleArgs& sa) { return sa.tau_dev ? *sa.tau_dev : sa.tau; }
+__device__ __forceinline__ float sat_sample_value(float x, float tau, float g) { return __fadd_rn(x, __fmul_rn(tau, g)); }
+// sat_argmax_rows drawing instead: out[b] (nullable: the next step's fed token), out2[b] (the sampled matrix), the
+// drawn token's embedding row (emb_out nullable)
+int sat_argmax_rows_sample(const void* X, int dtype, long ld, int B, int V, int32_t* out, long out_stride,
+                           int32_t* out2, long out2_stride, const float* emb, int E, void* emb_out, long emb_ld,
+                           const SatSampleArgs& sa, hipStream_t s);
+
 // ---- deterministic dense embedding gradient (nn.Embedding backward = index_add over the fed tokens, decoder.py:87,
 // 133): G[tok[r], :] += dX[r, :] as per-token sums in row order (one sort launch + a segment-sum launch + a fix-up
 // launch for tokens whose rows span several pieces), no fp32 atomics.  R <= sat_embed_sorted_max_rows(), V < 2^18.
@@ -96,6 +131,10 @@ struct HeadOutArgs {
   const bf16* w; const float* bias;           // [V][E], [V]
   bf16* preds; long preds_ld;
   float* pval; int32_t* pidx;
+  // the sample form (sat_decoder_forward_sample; a kernel instance of its own, the greedy one's code is unchanged):
+  // the partials are the per-block argmax of x + tau * G(seed, row, t, col) over the rounded logits
+  int sample;
+  SatSampleArgs smp;
 };
 int sat_greedy_head_out(const HeadOutArgs& a, hipStream_t s);
 // the number of argmax partials per row sat_greedy_head_out writes for these shapes (<= ceil(V / 16))

@@ -242,9 +242,14 @@ __global__ __launch_bounds__(NW * 64) void head_mid_kernel(HeadMidArgs a, int kw
 
 // vocabulary head of the step for all rows x 32 columns (K = E unsplit): act(x W^T + b) rounded to bf16 into preds,
 // and every row's argmax over the block's rounded logits into the partials
-template <int MB, int NW>
+// SMP: the sample form (HeadOutArgs::sample): each rounded logit competes as x + tau * G(seed, row, t, col)
+// (sat_internal.h); preds are the logits themselves, as in the greedy instance
+template <int MB, int NW, bool SMP = false>
 __global__ __launch_bounds__(NW * 64) void head_out_kernel(HeadOutArgs a, int kw, SatStamps st) {
   const SatStampT0 t0 = sat_stamp_begin(st);
+  uint64_t smp_seed = 0;
+  float tau = 0.f;
+  if constexpr (SMP) { smp_seed = sat_sample_seed(a.smp); tau = sat_sample_tau(a.smp); }
   __shared__ __attribute__((aligned(16))) float red[MB * 16 * SK_RLD];
   const int bx = blockIdx.x;
   // this thread's four bias columns (the same in every pass of the epilogue: NW * 64 is a multiple of 8), requested
@@ -273,7 +278,8 @@ __global__ __launch_bounds__(NW * 64) void head_out_kernel(HeadOutArgs a, int kw
       if (a.relu) x = x > 0.f ? x : 0.f;
       pv[k] = (bf16)x;
       if (row < a.B && col < a.V) {
-        const float xr = (float)pv[k];
+        float xr = (float)pv[k];
+        if constexpr (SMP) xr = sat_sample_value(xr, tau, sat_sample_gumbel(smp_seed, row, a.smp.t, col));
         if (sat_argmax_better(xr, col, best, bi)) { best = xr; bi = col; }
       }
     }
@@ -310,7 +316,7 @@ __global__ __launch_bounds__(NW * 64) void head_out_kernel(HeadOutArgs a, int kw
 // MFMAs of the first quarters run while the later ones land.  Argmax partials per 64 columns (the waves' per-row
 // winners meet in LDS).
 constexpr int HO_K = 512, HO_COLS = 64, HO_BLK = 64, HO_Q = 4, HO_QB = HO_K * 2 / HO_Q;   // 256-B quarter rows
-template <int MB>
+template <int MB, bool SMP = false>
 __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatStamps st) {
   static_assert(MB % 2 == 0, "DMA instructions cover 4 rows: MB * 16 / 4 per quarter, a multiple of the 4 waves");
   constexpr int MR = MB * 16, INSTR = MR / 4 / 4;   // DMA instructions per wave per quarter
@@ -379,6 +385,9 @@ __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatSta
     }
   });
   // lane holds columns n0 + 4 fh .. + 3 of row i * 16 + fr
+  uint64_t smp_seed = 0;
+  float tau = 0.f;
+  if constexpr (SMP) { smp_seed = sat_sample_seed(a.smp); tau = sat_sample_tau(a.smp); }   // the sample form, as above
   const bool vec = (a.V & 3) == 0 && (((uintptr_t)a.preds | (uintptr_t)(a.preds_ld * 2)) & 7) == 0;
 #pragma unroll
   for (int i = 0; i < MB; ++i) {
@@ -393,7 +402,8 @@ __global__ __launch_bounds__(256) void head_out_lds_kernel(HeadOutArgs a, SatSta
       if (a.relu) x = x > 0.f ? x : 0.f;
       pv[r] = (bf16)x;
       if (row < a.B && n + r < a.V) {
-        const float xr = (float)pv[r];
+        float xr = (float)pv[r];
+        if constexpr (SMP) xr = sat_sample_value(xr, tau, sat_sample_gumbel(smp_seed, row, a.smp.t, n + r));
         if (sat_argmax_better(xr, n + r, best, bi)) { best = xr; bi = n + r; }
       }
     }
@@ -500,10 +510,17 @@ int sat_greedy_head_blocks(int B, int V, int E) { return sat_cdiv(V, head_out_ld
 
 int sat_greedy_head_out(const HeadOutArgs& a, hipStream_t s) {
   if (!sat_greedy_supported(a.B, a.E) || a.V < 1) return (int)hipErrorInvalidValue;
+  if (a.sample && (a.V >= (1 << 20) || a.smp.t < 0 || a.smp.t >= (1 << 20))) return (int)hipErrorInvalidValue;
   const SatStamps st = sat_launch_stamps();
   if (head_out_lds(a.B, a.E)) {
     if (((uintptr_t)a.x & 15) || (a.x_ld & 7) || ((uintptr_t)a.w & 15)) return (int)hipErrorInvalidValue;
     const dim3 grid(sat_cdiv(a.V, HO_COLS));
+    if (a.sample) {
+      if (a.B <= 32) hipLaunchKernelGGL((head_out_lds_kernel<2, true>), grid, dim3(256), 0, s, a, st);
+      else if (a.B <= 64) hipLaunchKernelGGL((head_out_lds_kernel<4, true>), grid, dim3(256), 0, s, a, st);
+      else hipLaunchKernelGGL((head_out_lds_kernel<8, true>), grid, dim3(256), 0, s, a, st);
+      return (int)hipGetLastError();
+    }
     if (a.B <= 32) hipLaunchKernelGGL(head_out_lds_kernel<2>, grid, dim3(256), 0, s, a, st);
     else if (a.B <= 64) hipLaunchKernelGGL(head_out_lds_kernel<4>, grid, dim3(256), 0, s, a, st);
     else hipLaunchKernelGGL(head_out_lds_kernel<8>, grid, dim3(256), 0, s, a, st);
@@ -511,14 +528,20 @@ int sat_greedy_head_out(const HeadOutArgs& a, hipStream_t s) {
   }
   const dim3 grid(sat_cdiv(a.V, SK_COLS));
   const int nw = head_waves(a.E), kw = head_kw(a.E);
-#define SAT_HEAD_OUT(MB)                                                                                            \
+#define SAT_HEAD_OUT(MB, SMP)                                                                                       \
   do {                                                                                                            \
-    if (nw == 4) hipLaunchKernelGGL((head_out_kernel<MB, 4>), grid, dim3(256), 0, s, a, kw, st);                   \
-    else hipLaunchKernelGGL((head_out_kernel<MB, 8>), grid, dim3(512), 0, s, a, kw, st);                           \
+    if (nw == 4) hipLaunchKernelGGL((head_out_kernel<MB, 4, SMP>), grid, dim3(256), 0, s, a, kw, st);              \
+    else hipLaunchKernelGGL((head_out_kernel<MB, 8, SMP>), grid, dim3(512), 0, s, a, kw, st);                      \
   } while (0)
-  if (a.B <= 32) SAT_HEAD_OUT(2);
-  else if (a.B <= 64) SAT_HEAD_OUT(4);
-  else SAT_HEAD_OUT(8);
+  if (a.sample) {
+    if (a.B <= 32) SAT_HEAD_OUT(2, true);
+    else if (a.B <= 64) SAT_HEAD_OUT(4, true);
+    else SAT_HEAD_OUT(8, true);
+  } else {
+    if (a.B <= 32) SAT_HEAD_OUT(2, false);
+    else if (a.B <= 64) SAT_HEAD_OUT(4, false);
+    else SAT_HEAD_OUT(8, false);
+  }
 #undef SAT_HEAD_OUT
   return (int)hipGetLastError();
 }

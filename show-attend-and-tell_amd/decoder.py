@@ -126,6 +126,9 @@ class Decoder(nn.Module):
                                        # tf_prob: a captured step follows a decaying schedule without re-capture
         self.tf_mask = None            # test hook: uint8 keep-mask [B, T-1] (column 0 ignored) instead of the draw
         self.last_tf_mask = None       # uint8 [B, T-1]: the keep bits of the last sampled forward (record_tokens)
+        # sample(): optional 1-element float32 device tensor read by the kernels instead of the temperature argument
+        # (a captured step follows a temperature schedule without re-capture)
+        self.sample_temperature_tensor = None
 
     @property
     def tf_prob(self):
@@ -333,13 +336,16 @@ class Decoder(nn.Module):
         # dropout masks: host seed drawn once per module from torch's RNG (train.py:37-43 seeding)
         # XOR a device step counter the forward itself advances -> graph replays draw fresh masks
         if self.training:
-            if self._seed_host is None:
-                self._seed_host = _rank_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
-            if self._seed_dev is None or self._seed_dev.device != feats.device:
-                self._seed_dev = torch.zeros(1, dtype=torch.int64, device=feats.device)
-            d.seed = self._seed_host
-            d.seed_ptr = self._seed_dev.data_ptr()
+            self._seed_dims(d, feats.device)
         return d
+
+    def _seed_dims(self, d, device):
+        if self._seed_host is None:
+            self._seed_host = _rank_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        if self._seed_dev is None or self._seed_dev.device != device:
+            self._seed_dev = torch.zeros(1, dtype=torch.int64, device=device)
+        d.seed = self._seed_host
+        d.seed_ptr = self._seed_dev.data_ptr()
 
     def forward(self, img_features, captions):
         L.require_device(img_features, captions)
@@ -357,6 +363,55 @@ class Decoder(nn.Module):
             # backward and tags the gradient, so the decoder's backward skips its own mask pass
             preds._sat_relu_logits = True
         return preds, alphas
+
+    def sample(self, img_features, steps, temperature=1.0):
+        """Decode ``steps`` (= T-1 >= 2) steps feeding the decoder its own draws (sat_decoder_forward_sample): step 0
+        feeds the start token, step t >= 1 the token drawn at step t-1 from ``softmax(preds[:, t-1] / temperature)``
+        (Gumbel-max over the stored logits; temperature 0 is the greedy forward bit for bit).  Returns
+        ``(preds, alphas, sampled)``; ``preds`` / ``alphas`` are differentiable in the parameters and in
+        ``img_features`` (the fed tokens are constants, as in the greedy step), ``sampled`` [B, steps] int32 holds the
+        token drawn at every step, the last included.  Honours ``dropout_mask`` and ``policy``; ``eval()`` mode runs
+        without dropout and still draws.  The draw takes the dropout's seed and counter (each data-parallel rank its
+        own); ``sample_temperature_tensor``, when set, supplies the temperature from the device.  ``last_tokens``
+        is set as by ``forward``.  The module's ``use_tf`` is ignored."""
+        L.require_device(img_features)
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not float(temperature) >= 0.0:
+            raise ValueError(f"temperature must be a float >= 0, got {temperature!r}")   # also refuses NaN
+        steps = int(steps)
+        if steps < 2:
+            raise ValueError("sample: steps must be >= 2")
+        t_dev = self.sample_temperature_tensor
+        if t_dev is not None and (not isinstance(t_dev, torch.Tensor) or t_dev.dtype != torch.float32
+                                  or t_dev.numel() != 1 or t_dev.device != img_features.device):
+            raise ValueError("sample_temperature_tensor must be a 1-element float32 tensor on the features' device")
+        self._ensure_flat(img_features.device)
+        if img_features.dtype == torch.bfloat16:
+            self._ensure_lp()
+        if self._defer_phase2 and img_features.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("sat_amd.Decoder: img_features require grad while defer_recurrent_backward(True) is set")
+        params = [p for n, p in self.named_parameters()]
+        preds, alphas, sampled = _DecoderSampleFn.apply(img_features.contiguous(), (steps, float(temperature)), self,
+                                                        *params)
+        if self.use_advanced_deep_output:
+            preds._sat_relu_logits = True
+        return preds, alphas, sampled
+
+    def sample_noise(self, batch, steps, device=None):
+        """Diagnostic (sat_sample_noise): the noise ``G`` [batch, steps, V] fp32 the next ``sample`` call will add,
+        scaled by the temperature, to its logits.  Does not advance the counter."""
+        if device is None:
+            device = self._flat.device if self._flat is not None else torch.device("cuda")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("sat_amd: tensors must live on a HIP device (the product path has no CPU fallback)")
+        if device.index is None:   # the counter's device is compared with tensors' (always indexed)
+            device = torch.device("cuda", torch.cuda.current_device())
+        d = L.SatDecoderDims()
+        self._seed_dims(d, device)
+        out = torch.empty(int(batch), int(steps), self.vocabulary_size, device=device, dtype=torch.float32)
+        L.check(L.lib().sat_sample_noise(ctypes.byref(d), int(batch), int(steps), self.vocabulary_size, L.ptr(out),
+                                         L.stream_of(out)), "sat_sample_noise")
+        return out
 
     def caption(self, img_features, beam_size, max_step=50):
         """Beam search (decoder.py:160-269) as one C-ABI call (sat_decoder_beam_search).
@@ -609,3 +664,48 @@ class _DecoderFn(torch.autograd.Function):
         ctx.ws = None
         n_params = len(ctx.needs_input_grad) - 3
         return (d_feats, None, None) + (None,) * n_params
+
+
+class _DecoderSampleFn(torch.autograd.Function):
+    """Decoder.sample: sat_decoder_forward_sample, then _DecoderFn's backward on the same workspace."""
+
+    @staticmethod
+    def forward(ctx, feats, spec, dec, *params):
+        lib = L.lib()
+        steps, temperature = spec
+        dims = dec._dims(feats, torch.empty(1, steps + 1, dtype=torch.long))
+        dims.tf = 0
+        dec._seed_dims(dims, feats.device)   # eval mode draws too
+        lay = dec._layout()
+        ws_bytes = lib.sat_decoder_workspace_bytes(ctypes.byref(dims))
+        if ws_bytes == 0:
+            raise RuntimeError("sat_amd.Decoder: unsupported shape (E, D must be multiples of 8; L, E <= 1024; T >= 3)")
+        dev = feats.device
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        B, T1 = dims.B, dims.T - 1
+        preds = torch.empty(B, T1, dims.V, device=dev, dtype=feats.dtype)
+        alphas = torch.empty(B, T1, dims.L, device=dev, dtype=torch.float32)
+        tokens = torch.empty(B, T1, device=dev, dtype=torch.int32) if dec.record_tokens else None
+        sampled = torch.empty(B, T1, device=dev, dtype=torch.int32)
+        mask = None
+        if dims.has_dropout_mask:
+            mask = dec.dropout_mask.to(device=dev, dtype=torch.uint8).contiguous()
+            if tuple(mask.shape) != (B, T1, dims.E):
+                raise ValueError(f"dropout_mask must be [B, T-1, E] = {(B, T1, dims.E)}")
+        lp = dec._flat_lp if dims.dtype == L.SAT_BF16 else None
+        L.check(lib.sat_decoder_forward_sample(ctypes.byref(dims), ctypes.byref(lay), L.ptr(dec._flat), L.ptr(lp),
+                                               L.ptr(feats), None, L.ptr(mask), temperature,
+                                               L.ptr(dec.sample_temperature_tensor), L.ptr(ws), ws_bytes,
+                                               L.ptr(preds), L.ptr(alphas), L.ptr(tokens), L.ptr(sampled),
+                                               L.stream_of(preds)),
+                "sat_decoder_forward_sample")
+        dec.last_tf_mask = None
+        dec.last_tokens = tokens
+        ctx.dec, ctx.dims, ctx.lay, ctx.ws, ctx.ws_bytes, ctx.lp = dec, dims, lay, ws, ws_bytes, lp
+        ctx.save_for_backward(feats, preds, alphas)
+        ctx.mark_non_differentiable(sampled)
+        return preds, alphas, sampled
+
+    @staticmethod
+    def backward(ctx, d_preds, d_alphas, d_sampled):
+        return _DecoderFn.backward(ctx, d_preds, d_alphas)

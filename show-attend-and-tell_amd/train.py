@@ -38,6 +38,14 @@ so it cannot be disabled, as in train.py:450), plus:
                   dropout masks, a different draw per rank); validation and test follow --tf as before
   --tf-prob-end Q linear decay of that probability from P in epoch 1 to Q in the last epoch (default Q = P); the
                   epoch's value is logged as tf_prob
+  --scst          self-critical sequence training (Rennie et al. 2017), the stage after cross-entropy training (--model
+                  names the checkpoint to start from): per step a caption is sampled on the device
+                  (Decoder.sample), the greedy caption is decoded under no_grad, both are scored on the host and the
+                  policy gradient of (sample's reward - greedy's reward) is followed through the token-weighted
+                  loss; logs scst_reward_sample, scst_reward_greedy and scst_logp.  Not with --tf / --tf-prob
+  --scst-temperature T  temperature of the sampled caption (default 1.0)
+  --scst-reward   cider (default: CIDEr-D over token ids, document frequencies from the train split's references) |
+                  bleu (sentence BLEU-4 against the image's references)
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -62,6 +70,7 @@ if __package__ in (None, ""):
 else:
     import sat_amd  # noqa: E402
 from sat_amd import bleu as bleu_mod  # noqa: E402
+from sat_amd import cider as cider_mod  # noqa: E402
 from sat_amd import distributed as sat_dist  # noqa: E402
 from sat_amd.data import synthetic_captions, synthetic_images  # noqa: E402
 
@@ -194,7 +203,20 @@ def parse(argv=None):
                         "probability P and the model's own argmax otherwise (validation / test follow --tf)")
     p.add_argument("--tf-prob-end", type=float, default=None, metavar="Q",
                    help="with --tf-prob: linear decay from P in epoch 1 to Q in the last epoch (default: P)")
+    p.add_argument("--scst", action="store_true", default=False,
+                   help="self-critical sequence training: sample a caption, score it against the greedy caption's "
+                        "reward, follow the policy gradient (start from a cross-entropy checkpoint with --model)")
+    p.add_argument("--scst-temperature", type=float, default=1.0, metavar="T",
+                   help="with --scst: the temperature of the sampled caption")
+    p.add_argument("--scst-reward", choices=["cider", "bleu"], default="cider",
+                   help="with --scst: the sentence reward (CIDEr-D over token ids | sentence BLEU-4)")
     args = p.parse_args(argv)
+    if args.scst:
+        if args.tf or args.tf_prob is not None:
+            p.error("--scst samples the fed tokens from the model itself: it cannot be combined with --tf or "
+                    "--tf-prob")
+        if not args.scst_temperature >= 0.0:
+            p.error("--scst-temperature must be >= 0")
     if args.feature_cache:
         args.cache_features = True
     if args.tf_prob is None:
@@ -434,6 +456,105 @@ def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, l
     return meters.read()["loss"] if meters.last is not None else 0.0
 
 
+class ScstReward:
+    """The host reward of --scst: one float per caption (token ids) against the references of its image.  The
+    loader's third element, all_captions, only keys the references: CiderD is indexed by image."""
+
+    def __init__(self, args, dataset):
+        ids = cider_mod.BERT_IDS if args.bert else cider_mod.PLAIN_IDS
+        self.ids = (ids["start_id"], ids["end_id"], ids["pad_id"])
+        self.kind = args.scst_reward
+        if hasattr(dataset, "all_captions"):   # one entry per row; the rows of an image share the list
+            seen, refs = {}, []
+            for cs in dataset.all_captions:
+                key = self._key(cs)
+                if key not in seen:
+                    seen[key] = len(refs)
+                    refs.append(cs)
+        else:   # synthetic: one caption per image
+            refs = [[c] for c in dataset.caps.tolist()]
+            seen = {self._key(r): i for i, r in enumerate(refs)}
+        self.index = seen
+        self.cider = sat_amd.CiderD(refs, *self.ids)
+
+    @staticmethod
+    def _key(refs):
+        return tuple(tuple(int(t) for t in r) for r in refs)
+
+    def __call__(self, captions, all_caps):
+        images = [self.index[self._key(r)] for r in all_caps]
+        if self.kind == "cider":
+            return self.cider.score(captions, images)
+        strip = lambda c: [str(t) for t in cider_mod.strip_ids(c, *self.ids)]  # noqa: E731
+        out = []
+        for c, i in zip(captions, images):
+            hyp = strip(c)
+            out.append(float(bleu_mod.corpus_bleu([[strip(r) for r in self.cider.refs[i]]], [hyp])) if hyp else 0.0)
+        return out
+
+
+def scst_batches(loader, encoder, cache, device, dt, max_steps):
+    """(batch_idx, features, all_captions) of every training batch, the trunk (or its cached output) under no_grad
+    except for a fine-tuned tail."""
+    k = encoder.tail_start() if getattr(encoder, "_fine_tune", 0) else None
+    for batch_idx, (imgs, _, all_caps) in enumerate(loader):
+        if max_steps and batch_idx >= max_steps:
+            break
+        with torch.no_grad():
+            if cache is not None:
+                feats = cache.gather(cache.slots[imgs])
+            elif k is None:
+                feats = encoder(imgs.to(device, non_blocking=True), dtype=dt)
+            else:
+                feats = encoder(imgs.to(device, non_blocking=True), dtype=dt, steps=(0, k))
+        if k is not None:
+            feats = encoder(feats, dtype=dt, steps=(k, encoder._plan_len()))
+        yield batch_idx, feats, all_caps.tolist()
+
+
+def scst_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, log, reward, grad_ar=None, cache=None):
+    """One epoch of self-critical sequence training.  Per step: a sample-mode forward in train mode, a greedy forward
+    under no_grad in eval mode, both token matrices to the host in one copy, the rewards, advantage = r_sample -
+    r_greedy, the token-weighted loss, backward, the optimizer step."""
+    encoder.eval()
+    end_id = reward.ids[1]
+    sums, n_logged, last = [0.0, 0.0], 0, 0.0
+    for batch_idx, feats, all_caps in scst_batches(loader, encoder, cache, device, dt, args.max_steps):
+        B = feats.shape[0]
+        steps = len(all_caps[0][0]) - 1
+        opt.zero_grad()
+        decoder.train()
+        preds, alphas, sampled = decoder.sample(feats, steps, temperature=args.scst_temperature)
+        decoder.eval()
+        with torch.no_grad():
+            greedy = decoder.sample(feats.detach(), steps, temperature=0.0)[2]   # temperature 0: the greedy forward
+        decoder.train()
+        both = torch.cat([sampled, greedy]).cpu().tolist()   # the one device-to-host copy of the step
+        r_sample, r_greedy = reward(both[:B], all_caps), reward(both[B:], all_caps)
+        advantage = torch.tensor([a - b for a, b in zip(r_sample, r_greedy)], dtype=torch.float32, device=device)
+        w = sat_amd.scst_weights(sampled, advantage, (end_id,))
+        loss, logp = sat_amd.weighted_caption_loss(preds, alphas, sampled, w, 0.0)
+        loss.backward()
+        if grad_ar is not None:
+            grad_ar.wait()
+            if args.fine_tune_encoder:
+                sat_dist.all_reduce_tail_grads(encoder)
+        opt.step()
+        sums[0] += sum(r_sample) / B
+        sums[1] += sum(r_greedy) / B
+        n_logged += 1
+        if batch_idx % args.log_interval == 0:
+            # the sampled sentences' positions (up to and including the first end token), whatever their advantage
+            scored = sat_amd.scst_weights(sampled, torch.full((B,), float(B), device=device), (end_id,))
+            mean_logp = float((logp * scored).sum() / scored.sum().clamp_min(1))
+            last = float(loss)
+            log(dict(epoch=epoch, batch=batch_idx, train_loss=last, scst_reward_sample=sums[0] / n_logged,
+                     scst_reward_greedy=sums[1] / n_logged, scst_logp=mean_logp))
+    if cache is not None:
+        cache.check_bad_rows()
+    return last
+
+
 def evaluate(epoch, encoder, decoder, loader, args, device, dt, word_dict, mode, log, cache=None):
     """train.py:198-347 (teacher-forced greedy hypotheses, BLEU-1..4); with --beam-eval K also the BLEU of the
     sentences batched beam search generates from the same features.  ``cache``: the split's FeatureCache (``loader``
@@ -513,6 +634,9 @@ def main(argv=None):
         if rank == 0:
             print(json.dumps(rec), flush=True)
 
+    if args.scst and not args.model:
+        print("WARNING: --scst without --model: self-critical training is the stage after cross-entropy training and "
+              "starts here from a randomly initialised decoder", file=sys.stderr, flush=True)
     encoder, decoder, word_dict, dt = build(args, device)
     decoder.record_tokens = False   # no fed-token record per training step
     if not args.no_overlap:   # the decoder shares the chip with the next batch's encoder (bench.py defaults)
@@ -533,6 +657,7 @@ def main(argv=None):
             caches[split] = build_feature_cache(args, split, encoder, device, dt, rank, world, log)
     train_loader = loaders(args, "train", rank, world, captions_only=args.cache_features)
     val_loader = loaders(args, "val", rank, world, captions_only=args.cache_features)
+    reward = ScstReward(args, train_loader.dataset) if args.scst else None
     os.makedirs(args.out, exist_ok=True)
     enc_path = os.path.join(args.out, f"encoder_{args.network}.pth")
     if rank == 0:   # the trunk this run uses, so generate_caption.py encodes with the same weights
@@ -543,8 +668,12 @@ def main(argv=None):
             train_loader.sampler.set_epoch(epoch)
         if args.tf_prob is not None:   # scheduled sampling: set once per epoch (eval mode ignores it)
             decoder.tf_prob = tf_prob_schedule(epoch, args.epochs, args.tf_prob, args.tf_prob_end)
-        train_epoch(epoch, encoder, decoder, opt, train_loader, args, device, dt, world, log, grad_ar,
-                    caches.get("train"))
+        if args.scst:
+            scst_epoch(epoch, encoder, decoder, opt, train_loader, args, device, dt, log, reward, grad_ar,
+                       caches.get("train"))
+        else:
+            train_epoch(epoch, encoder, decoder, opt, train_loader, args, device, dt, world, log, grad_ar,
+                        caches.get("train"))
         evaluate(epoch, encoder, decoder, val_loader, args, device, dt, word_dict, "val", log, caches.get("val"))
         sched.step()
         if rank == 0:   # train.py:103-110
