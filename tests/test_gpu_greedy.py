@@ -78,8 +78,10 @@ def _greedy_seeded(sat, c, form):
 # bit-reproducible run to run, but with dropout drawn from the decoder's seed the error depends on the
 # draw: where a draw flips a bf16 rounding of a per-step operand the head and LSTM gradients move by up to 2.9e-2
 # ([True-1], profiles/r6_s70: torch's default generator is seeded per process here, so each process drew other
-# masks; profiles/r6_s71: 1 of 3 processes) -- hence 3e-2, and _greedy_seeded now fixes the draw
-MIRROR_TOL = 3e-2
+# masks; profiles/r6_s71: 1 of 3 processes), which the bound was once sized for (3e-2).  _greedy_seeded fixes the
+# draw, so the bound is the worst figure measured again with it over the five cases that use it (2.66e-3,
+# attention.W.weight of the odd-vocabulary case; the seeded cases <= 2.31e-3: profiles/batch_classes/measured.txt) x 2
+MIRROR_TOL = 5.3e-3
 
 
 def _mirror_fed(c, tokens):

@@ -5,8 +5,8 @@ The golden fixtures (test_gpu_parity.py) pin the oracle against the reference at
 L <= 16, V <= 128; these tests carry that parity to the production kernel instances:
 
   * ResNet152 decoder: D = 2048, L = 49, E = 512, V = 10000, --ado --attention --tf (cfg2/cfg3;
-    attention forward over several D-slices, the DCH = 4 one-launch attention backward in bf16 and
-    the two-launch fp32 fallback at D = 2048);
+    attention forward over several D-slices, the one-launch attention backward with DCH = 4 in bf16 and
+    DCH = 8 in fp32 -- sat_decoder_instance reports its chunks, not the two-launch form's 0, for both);
   * VGG19 + BERT decoder: D = 512, L = 196, E = 768, V = 30522 (odd vocabulary), simple head (cfg5);
   * VGG19 greedy decoder: D = 512, L = 196, E = 512, V = 2600, --tf off (cfg1 shapes, cfg4 feedback);
   * teacher-forced BLEU at the ResNet eval shape (L = 49, V = 10000, T = 27);
