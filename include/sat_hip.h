@@ -616,6 +616,45 @@ int sat_rows_gather(const void* table, int64_t n_rows, int64_t row_elems, int dt
 int sat_rows_scatter(const void* src, int n, int64_t row_elems, int dtype, const int64_t* idx, void* table,
                      int64_t n_rows, int32_t* n_bad, void* stream);
 
+/* --- CIDEr-D on the device (the reward of self-critical sequence training; the arithmetic of sat_amd/cider.py) ----
+ * The corpus is resident, built once, all device arrays:
+ *   table          slots x 4 uint32 (16-B aligned, zeroed by the caller before the first insert): an open-addressed
+ *                  hash table from n-gram to idf = log N - log max(1, df), fp32.  A slot is the 96-bit key and the
+ *                  value; slots in [2, 2^31), any number (not only powers of two), at least one left empty.
+ *   key            3 uint32 per n-gram (ids g0..g(n-1), each below 2^20, n = 1..4, the ids past n zero):
+ *                    word 0 = n << 20 | g0,  word 1 = g1 | (g2 & 0xfff) << 20,  word 2 = g2 >> 12 | g3 << 8
+ *                  The key holds the whole n-gram and n: a hash collision costs a probe, never a value.
+ *   ref_words      int32 [n_refs, ref_stride] the stripped reference sentences, ref_len[n_refs] their lengths
+ *   img_ref_begin  int32 [n_images + 1]: image i owns references img_ref_begin[i] .. img_ref_begin[i + 1] - 1
+ *   ref_norm       float [n_refs, 4]: the norm of every reference's tf-idf vector per n
+ * A key absent from the table has df 0 and idf log_n.  Every probe loop ends after `slots` probes.
+ *
+ * sat_cider_table_insert: stores n keys with their values.  The keys are unique among themselves and against the
+ *   table's contents (they come from one document-frequency dictionary); lookups belong in later launches.  A key that
+ *   finds no empty slot, or whose word 0 is 0, adds 1 to *n_bad (device, nullable, zeroed by the caller).
+ * sat_cider_lookup: out[i] = the value stored under keys[3 i .. 3 i + 2], log_n for an absent key (a diagnostic, and
+ *   the lookup the two kernels below use).
+ * sat_cider_ref_norms: fills ref_norm from ref_words / ref_len with the scorer's own counting and lookup code.
+ * sat_cider_score: out[i] = CIDEr-D of tokens[i, 0 .. T1) against the references of image[i]: start and pad ids are
+ *   dropped wherever they stand and the sentence ends before the first end id; sigma = 6, the mean over n = 1..4 and
+ *   over the references, times 10; an empty sentence or an image without references scores 0.  One wave per row; a
+ *   row's score depends on that row only and reductions run in a fixed order (bit-identical reruns).  tokens
+ *   [n, T1] int32, image [n] int64 and out [n] are read and written on the device when the launch runs: the call is
+ *   capturable.  An image index outside [0, n_images) scores 0 and adds 1 to *n_bad (device, nullable); a token
+ *   outside [0, 2^20) is a word no reference has.
+ * T1 or ref_stride outside [1, 64], slots outside [2, 2^31), a table not 16-B aligned, a null array or a negative
+ * count: SAT_ERR_INVALID before any launch; n == 0 (n_refs == 0 for the norms) is a successful no-op. */
+int sat_cider_table_insert(uint32_t* table, int64_t slots, const uint32_t* keys, const float* values, int64_t n,
+                           int32_t* n_bad, void* stream);
+int sat_cider_lookup(const uint32_t* table, int64_t slots, float log_n, const uint32_t* keys, int64_t n, float* out,
+                     void* stream);
+int sat_cider_ref_norms(const uint32_t* table, int64_t slots, float log_n, const int32_t* ref_words,
+                        const int32_t* ref_len, int n_refs, int ref_stride, float* ref_norm, void* stream);
+int sat_cider_score(const uint32_t* table, int64_t slots, float log_n, const int32_t* ref_words,
+                    const int32_t* ref_len, const float* ref_norm, int n_refs, int ref_stride,
+                    const int32_t* img_ref_begin, int n_images, const int32_t* tokens, const int64_t* image, int n,
+                    int T1, int start_id, int end_id, int pad_id, float* out, int32_t* n_bad, void* stream);
+
 /* --- optimiser (torch.optim.Adam single-tensor step, train.py:71,164) ---- */
 int sat_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                   void* param_lp, int64_t n, float beta1, float beta2, float eps,

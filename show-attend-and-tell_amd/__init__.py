@@ -9,6 +9,7 @@ from . import _lib
 from ._lib import SatPolicy as Policy
 from .attention import Attention
 from .cider import CiderD
+from .cider_device import CiderDDevice
 from .data import PackedImages, collate_packed
 from .decoder import Decoder
 from .encoder import Encoder
@@ -18,4 +19,5 @@ from .loss import (caption_loss, special_ids, StepMetrics, RunningMeters, weight
 from .optim import Adam
 
 __all__ = ["Attention", "Decoder", "Encoder", "caption_loss", "special_ids", "StepMetrics", "RunningMeters", "Adam",
-           "PackedImages", "collate_packed", "FeatureCache", "weighted_caption_loss", "scst_weights", "CiderD"]
+           "PackedImages", "collate_packed", "FeatureCache", "weighted_caption_loss", "scst_weights", "CiderD",
+           "CiderDDevice"]

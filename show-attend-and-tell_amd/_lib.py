@@ -223,6 +223,13 @@ _SIGNATURES = [
                                     c_void_p, c_size_t, c_void_p]),
     ("sat_rows_gather", c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     ("sat_rows_scatter", c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    ("sat_cider_table_insert", c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    ("sat_cider_lookup", c_int, [c_void_p, c_int64, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    ("sat_cider_ref_norms", c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                    c_void_p]),
+    ("sat_cider_score", c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p]),
     ("sat_adam_step", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
                               c_float, c_float, c_float, c_void_p]),
 ]

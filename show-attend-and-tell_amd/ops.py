@@ -522,6 +522,116 @@ def rows_scatter(src, idx, table, n_bad=None):
     return table
 
 
+CIDER_MAX_WORDS = 64        # words of a hypothesis row / a reference the device scorer takes
+CIDER_ID_LIMIT = 1 << 20    # token ids are below this (the sampling entries' limit)
+
+
+def _cider_table_args(what, table):
+    L.require_device(table)
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 2 \
+            or not table.is_contiguous():
+        raise ValueError(f"{what}: table must be a contiguous int32 [slots, 4] tensor with slots >= 2")
+    return table.shape[0]
+
+
+def _cider_keys_args(what, table, keys, other, other_dtype):
+    L.require_device(keys, other)
+    if keys.dtype != torch.int32 or keys.dim() != 2 or keys.shape[1] != 3 or not keys.is_contiguous() \
+            or keys.device != table.device:
+        raise ValueError(f"{what}: keys must be a contiguous int32 [n, 3] tensor on the table's device")
+    if other.dtype != other_dtype or tuple(other.shape) != (keys.shape[0],) or not other.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {other_dtype} vector of {keys.shape[0]} elements")
+
+
+def cider_table_insert(table, keys, values, n_bad=None):
+    """Store the packed n-gram ``keys`` (int32 [n, 3], the bit pattern of sat_hip.h's key words; unique) with their fp32
+    ``values`` in ``table`` (int32 [slots, 4], zeroed before the first insert).  A key that finds no slot adds 1 to
+    ``n_bad`` (one int32 on the device)."""
+    slots = _cider_table_args("cider_table_insert", table)
+    _cider_keys_args("cider_table_insert", table, keys, values, torch.float32)
+    L.require_device(n_bad)
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1):
+        raise ValueError("cider_table_insert: n_bad must be one int32")
+    if keys.shape[0]:
+        L.check(L.lib().sat_cider_table_insert(L.ptr(table), slots, L.ptr(keys), L.ptr(values), keys.shape[0],
+                                               L.ptr(n_bad), L.stream_of(table)), "sat_cider_table_insert")
+    return table
+
+
+def cider_lookup(table, log_n, keys, out=None):
+    """out[i] = the value stored under keys[i], ``log_n`` for a key that was never inserted (sat_cider_lookup)."""
+    slots = _cider_table_args("cider_lookup", table)
+    if out is None:
+        L.require_device(keys)
+        out = torch.empty(keys.shape[0], device=keys.device, dtype=torch.float32)
+    _cider_keys_args("cider_lookup", table, keys, out, torch.float32)
+    if keys.shape[0]:
+        L.check(L.lib().sat_cider_lookup(L.ptr(table), slots, float(log_n), L.ptr(keys), keys.shape[0], L.ptr(out),
+                                         L.stream_of(out)), "sat_cider_lookup")
+    return out
+
+
+def _cider_refs_args(what, table, ref_words, ref_len, ref_norm):
+    L.require_device(ref_words, ref_len, ref_norm)
+    n_refs = ref_len.shape[0] if ref_len.dim() == 1 else -1
+    if ref_words.dtype != torch.int32 or ref_words.dim() != 2 or not ref_words.is_contiguous() \
+            or ref_words.shape[0] < max(1, n_refs) or not 1 <= ref_words.shape[1] <= CIDER_MAX_WORDS:
+        raise ValueError(f"{what}: ref_words must be a contiguous int32 [n_refs, stride <= {CIDER_MAX_WORDS}] tensor")
+    if ref_len.dtype != torch.int32 or n_refs < 0 or not ref_len.is_contiguous():
+        raise ValueError(f"{what}: ref_len must be a contiguous int32 vector")
+    if ref_norm.dtype != torch.float32 or ref_norm.dim() != 2 or ref_norm.shape[1] != 4 \
+            or ref_norm.shape[0] < max(1, n_refs) or not ref_norm.is_contiguous():
+        raise ValueError(f"{what}: ref_norm must be a contiguous float32 [n_refs, 4] tensor")
+    if not (ref_words.device == ref_len.device == ref_norm.device == table.device):
+        raise ValueError(f"{what}: the corpus tensors must live on one device")
+    return n_refs, ref_words.shape[1]
+
+
+def cider_ref_norms(table, log_n, ref_words, ref_len, ref_norm):
+    """ref_norm[r, n - 1] = the norm of reference r's tf-idf vector of n-grams (sat_cider_ref_norms)."""
+    slots = _cider_table_args("cider_ref_norms", table)
+    n_refs, stride = _cider_refs_args("cider_ref_norms", table, ref_words, ref_len, ref_norm)
+    if n_refs:
+        L.check(L.lib().sat_cider_ref_norms(L.ptr(table), slots, float(log_n), L.ptr(ref_words), L.ptr(ref_len),
+                                            n_refs, stride, L.ptr(ref_norm), L.stream_of(ref_norm)),
+                "sat_cider_ref_norms")
+    return ref_norm
+
+
+def cider_score(table, log_n, ref_words, ref_len, ref_norm, img_ref_begin, tokens, image, ids, out=None, n_bad=None):
+    """CIDEr-D of every row of ``tokens`` (int32 [n, T1 <= 64], device) against the references of ``image`` (int64
+    [n], device) -> float32 [n] (sat_cider_score); ``ids`` = (start, end, pad).  No host read: capturable."""
+    slots = _cider_table_args("cider_score", table)
+    n_refs, stride = _cider_refs_args("cider_score", table, ref_words, ref_len, ref_norm)
+    L.require_device(img_ref_begin, tokens, image, n_bad)
+    if img_ref_begin.dtype != torch.int32 or img_ref_begin.dim() != 1 or img_ref_begin.shape[0] < 1 \
+            or not img_ref_begin.is_contiguous() or img_ref_begin.device != table.device:
+        raise ValueError("cider_score: img_ref_begin must be a contiguous int32 [n_images + 1] vector")
+    if tokens.dtype != torch.int32 or tokens.dim() != 2 or not tokens.is_contiguous() \
+            or not 1 <= tokens.shape[1] <= CIDER_MAX_WORDS or tokens.device != table.device:
+        raise ValueError(f"cider_score: tokens must be a contiguous int32 [n, T1] tensor on the corpus' device with "
+                         f"1 <= T1 <= {CIDER_MAX_WORDS}, got {tokens.dtype} {tuple(tokens.shape)}")
+    if image.dtype != torch.int64 or tuple(image.shape) != (tokens.shape[0],) or not image.is_contiguous() \
+            or image.device != table.device:
+        raise ValueError(f"cider_score: image must be a contiguous int64 vector of {tokens.shape[0]} elements on the "
+                         f"corpus' device, got {image.dtype} {tuple(image.shape)}")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1):
+        raise ValueError("cider_score: n_bad must be one int32")
+    if out is None:
+        out = torch.empty(tokens.shape[0], device=tokens.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (tokens.shape[0],) or not out.is_contiguous() \
+            or out.device != table.device:
+        raise ValueError("cider_score: out must be a contiguous float32 [n] tensor on the corpus' device")
+    if tokens.shape[0]:
+        start_id, end_id, pad_id = (int(i) for i in ids)
+        L.check(L.lib().sat_cider_score(L.ptr(table), slots, float(log_n), L.ptr(ref_words), L.ptr(ref_len),
+                                        L.ptr(ref_norm), n_refs, stride, L.ptr(img_ref_begin),
+                                        img_ref_begin.shape[0] - 1, L.ptr(tokens), L.ptr(image), tokens.shape[0],
+                                        tokens.shape[1], start_id, end_id, pad_id, L.ptr(out), L.ptr(n_bad),
+                                        L.stream_of(out)), "sat_cider_score")
+    return out
+
+
 def adam_step_(param, grad, exp_avg, exp_avg_sq, param_lp, beta1, beta2, eps, step_size, bc2_sqrt):
     L.check(L.lib().sat_adam_step(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), L.ptr(param_lp),
                                   param.numel(), beta1, beta2, eps, step_size, bc2_sqrt, L.stream_of(param)),

@@ -45,7 +45,10 @@ so it cannot be disabled, as in train.py:450), plus:
                   loss; logs scst_reward_sample, scst_reward_greedy and scst_logp.  Not with --tf / --tf-prob
   --scst-temperature T  temperature of the sampled caption (default 1.0)
   --scst-reward   cider (default: CIDEr-D over token ids, document frequencies from the train split's references) |
-                  bleu (sentence BLEU-4 against the image's references)
+                  bleu (sentence BLEU-4 against the image's references) | cider-device (the same CIDEr-D scored on the
+                  device by sat_amd.CiderDDevice: the references, their norms and the n-gram table are resident in HBM,
+                  the token matrices never leave the device, the advantage is a device subtraction and the step has no
+                  device-to-host copy; the logged reward sums live on the device and are read on --log-interval steps)
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -208,8 +211,9 @@ def parse(argv=None):
                         "reward, follow the policy gradient (start from a cross-entropy checkpoint with --model)")
     p.add_argument("--scst-temperature", type=float, default=1.0, metavar="T",
                    help="with --scst: the temperature of the sampled caption")
-    p.add_argument("--scst-reward", choices=["cider", "bleu"], default="cider",
-                   help="with --scst: the sentence reward (CIDEr-D over token ids | sentence BLEU-4)")
+    p.add_argument("--scst-reward", choices=["cider", "bleu", "cider-device"], default="cider",
+                   help="with --scst: the sentence reward (CIDEr-D over token ids | sentence BLEU-4 | the same CIDEr-D "
+                        "scored on the device: no host round trip in the step)")
     args = p.parse_args(argv)
     if args.scst:
         if args.tf or args.tf_prob is not None:
@@ -458,9 +462,10 @@ def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, l
 
 class ScstReward:
     """The host reward of --scst: one float per caption (token ids) against the references of its image.  The
-    loader's third element, all_captions, only keys the references: CiderD is indexed by image."""
+    loader's third element, all_captions, only keys the references: CiderD is indexed by image.  With --scst-reward
+    cider-device it also holds the corpus on the device (``device_cider``) and the image of every dataset row."""
 
-    def __init__(self, args, dataset):
+    def __init__(self, args, dataset, device=None):
         ids = cider_mod.BERT_IDS if args.bert else cider_mod.PLAIN_IDS
         self.ids = (ids["start_id"], ids["end_id"], ids["pad_id"])
         self.kind = args.scst_reward
@@ -476,6 +481,20 @@ class ScstReward:
             seen = {self._key(r): i for i, r in enumerate(refs)}
         self.index = seen
         self.cider = sat_amd.CiderD(refs, *self.ids)
+        self.device_cider = self.row_image = None
+        if self.kind == "cider-device":   # the corpus resident on the device, and the image of every dataset row
+            self.device_cider = sat_amd.CiderDDevice(self.cider, device)
+            rows = dataset.all_captions if hasattr(dataset, "all_captions") else refs
+            self.row_image = torch.tensor([seen[self._key(cs)] for cs in rows], dtype=torch.int64, device=device)
+
+    def images(self, all_caps, rows, device):
+        """The image index of every row of the batch as an int64 device vector: from the loader's dataset rows when it
+        hands them over (--cache-features), else by the host lookup of the rows' reference lists -- which depends on
+        nothing the device computed, so neither waits for it."""
+        if rows is not None:
+            return self.row_image[rows.to(device, non_blocking=True)]
+        return torch.tensor([self.index[self._key(r)] for r in all_caps.tolist()], dtype=torch.int64).to(
+            device, non_blocking=True)
 
     @staticmethod
     def _key(refs):
@@ -494,8 +513,8 @@ class ScstReward:
 
 
 def scst_batches(loader, encoder, cache, device, dt, max_steps):
-    """(batch_idx, features, all_captions) of every training batch, the trunk (or its cached output) under no_grad
-    except for a fine-tuned tail."""
+    """(batch_idx, features, all_captions, dataset rows) of every training batch, the trunk (or its cached output) under
+    no_grad except for a fine-tuned tail.  The rows are the loader's when it yields them (a cache), else None."""
     k = encoder.tail_start() if getattr(encoder, "_fine_tune", 0) else None
     for batch_idx, (imgs, _, all_caps) in enumerate(loader):
         if max_steps and batch_idx >= max_steps:
@@ -509,19 +528,25 @@ def scst_batches(loader, encoder, cache, device, dt, max_steps):
                 feats = encoder(imgs.to(device, non_blocking=True), dtype=dt, steps=(0, k))
         if k is not None:
             feats = encoder(feats, dtype=dt, steps=(k, encoder._plan_len()))
-        yield batch_idx, feats, all_caps.tolist()
+        yield batch_idx, feats, all_caps, imgs if cache is not None else None
 
 
 def scst_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, log, reward, grad_ar=None, cache=None):
     """One epoch of self-critical sequence training.  Per step: a sample-mode forward in train mode, a greedy forward
     under no_grad in eval mode, both token matrices to the host in one copy, the rewards, advantage = r_sample -
-    r_greedy, the token-weighted loss, backward, the optimizer step."""
+    r_greedy, the token-weighted loss, backward, the optimizer step.  With --scst-reward cider-device both token
+    matrices are scored where they are (one launch), the advantage is a device subtraction and nothing is copied to the
+    host; the reward sums of the log accumulate in a device tensor that is read on --log-interval steps only."""
     encoder.eval()
     end_id = reward.ids[1]
+    on_device = reward.device_cider is not None
     sums, n_logged, last = [0.0, 0.0], 0, 0.0
-    for batch_idx, feats, all_caps in scst_batches(loader, encoder, cache, device, dt, args.max_steps):
+    sums_dev = torch.zeros(2, dtype=torch.float64, device=device) if on_device else None
+    for batch_idx, feats, all_caps, rows in scst_batches(loader, encoder, cache, device, dt, args.max_steps):
         B = feats.shape[0]
-        steps = len(all_caps[0][0]) - 1
+        steps = all_caps.shape[2] - 1
+        if not on_device:
+            all_caps = all_caps.tolist()
         opt.zero_grad()
         decoder.train()
         preds, alphas, sampled = decoder.sample(feats, steps, temperature=args.scst_temperature)
@@ -529,9 +554,14 @@ def scst_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, log, rewa
         with torch.no_grad():
             greedy = decoder.sample(feats.detach(), steps, temperature=0.0)[2]   # temperature 0: the greedy forward
         decoder.train()
-        both = torch.cat([sampled, greedy]).cpu().tolist()   # the one device-to-host copy of the step
-        r_sample, r_greedy = reward(both[:B], all_caps), reward(both[B:], all_caps)
-        advantage = torch.tensor([a - b for a, b in zip(r_sample, r_greedy)], dtype=torch.float32, device=device)
+        if on_device:
+            images = reward.images(all_caps, rows, device)
+            r = reward.device_cider.score(torch.cat([sampled, greedy]), torch.cat([images, images]))
+            advantage = r[:B] - r[B:]
+        else:
+            both = torch.cat([sampled, greedy]).cpu().tolist()   # the one device-to-host copy of the step
+            r_sample, r_greedy = reward(both[:B], all_caps), reward(both[B:], all_caps)
+            advantage = torch.tensor([a - b for a, b in zip(r_sample, r_greedy)], dtype=torch.float32, device=device)
         w = sat_amd.scst_weights(sampled, advantage, (end_id,))
         loss, logp = sat_amd.weighted_caption_loss(preds, alphas, sampled, w, 0.0)
         loss.backward()
@@ -540,10 +570,15 @@ def scst_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, log, rewa
             if args.fine_tune_encoder:
                 sat_dist.all_reduce_tail_grads(encoder)
         opt.step()
-        sums[0] += sum(r_sample) / B
-        sums[1] += sum(r_greedy) / B
+        if on_device:
+            sums_dev += r.double().view(2, B).sum(1) / B
+        else:
+            sums[0] += sum(r_sample) / B
+            sums[1] += sum(r_greedy) / B
         n_logged += 1
         if batch_idx % args.log_interval == 0:
+            if on_device:
+                sums = sums_dev.tolist()
             # the sampled sentences' positions (up to and including the first end token), whatever their advantage
             scored = sat_amd.scst_weights(sampled, torch.full((B,), float(B), device=device), (end_id,))
             mean_logp = float((logp * scored).sum() / scored.sum().clamp_min(1))
@@ -552,6 +587,8 @@ def scst_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, log, rewa
                      scst_reward_greedy=sums[1] / n_logged, scst_logp=mean_logp))
     if cache is not None:
         cache.check_bad_rows()
+    if on_device:
+        reward.device_cider.check_bad_images()   # one host read per epoch, as the cache's
     return last
 
 
@@ -657,7 +694,7 @@ def main(argv=None):
             caches[split] = build_feature_cache(args, split, encoder, device, dt, rank, world, log)
     train_loader = loaders(args, "train", rank, world, captions_only=args.cache_features)
     val_loader = loaders(args, "val", rank, world, captions_only=args.cache_features)
-    reward = ScstReward(args, train_loader.dataset) if args.scst else None
+    reward = ScstReward(args, train_loader.dataset, device) if args.scst else None
     os.makedirs(args.out, exist_ok=True)
     enc_path = os.path.join(args.out, f"encoder_{args.network}.pth")
     if rank == 0:   # the trunk this run uses, so generate_caption.py encodes with the same weights
