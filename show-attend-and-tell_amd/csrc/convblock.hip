@@ -12,7 +12,7 @@
 //     c1 is computed for the 8 image rows c2 needs (its one-row halo), c1 and c2 outputs never
 //     leave LDS (X1: c1 rows + a zero row, X2: c2 rows, both bf16 in 64-channel planes of 128-B
 //     rows, 16-B chunk c of row r at slot c ^ (r & 7): conflict-free ds_read_b128 for every 3x3
-//     row shift, as in convhalo.hip);
+//     row shift);
 //   * 8 waves, each owning 32 output channels of the current 256-wide phase (n-blocks 2w, 2w+1) and
 //     all 7 16-row m-blocks; MFMA v_mfma_f32_16x16x32_bf16 computes C^T = W . X^T, so a lane holds
 //     4 consecutive channels of one pixel: epilogues write 8-byte pieces (X1 / X2 / global) without
@@ -29,6 +29,12 @@
 // Arithmetic: each conv sums its K in the same order as the unfused kernels (k-tiles ascending, c2
 // tap-major), adds the folded bias in fp32, applies ReLU and rounds to bf16 once; c3 adds the residual
 // in fp32 before the ReLU -- bit-identical to the three-launch path (tests/test_gpu_parity.py).
+//
+// The same file holds the block's phases as convs of their own (the 3x3 half-image, band and whole-image
+// forms, the 1x1 half-image form).  Every body keeps its own schedule -- what is staged in LDS, the issue
+// order of DMAs and weight loads and the vmcnt waits that count them -- and shares the pieces that do not
+// depend on it: the weight-fragment loader, the k-tile's fragment reads + MFMAs, the 3x3 tap offsets and
+// the global-store epilogue.
 #include "sat_common.h"
 #include "sat_internal.h"
 #include "sat_lds_pipe.h"
@@ -52,8 +58,8 @@ struct KArgs {
 
 // vmem instructions one wave issues after its input DMAs A(T) (na instructions) and before the wait
 // of c1 k-tile T: the issue order is A0 B0 A1 B1 B2 .. B(PF-1) (B = nb weight loads), then per k-tile
-// it, after its wait: A(it+2) (it+2 < KT1), B(it+PF) (it+PF < NT, when weights stream)
-constexpr int younger_than_a(int T, int KT1, int NT, int PF, bool stream, int nb = 4, int na = 2) {
+// it, after its wait: A(it+2) (it+2 < KT1), B(it+PF) (it+PF < NT)
+constexpr int younger_than_a(int T, int KT1, int NT, int PF, int nb = 4, int na = 2) {
   int n = 0;
   bool after = false;
   auto ev_a = [&](int idx) {
@@ -67,13 +73,13 @@ constexpr int younger_than_a(int T, int KT1, int NT, int PF, bool stream, int nb
   for (int e = 2; e < PF; ++e) ev_b();
   for (int it = 0; it < T; ++it) {
     if (it + 2 < KT1) ev_a(it + 2);
-    if (stream && it + PF < NT) ev_b();
+    if (it + PF < NT) ev_b();
   }
   return n;
 }
 
 // the same count for a ring whose input DMAs run `da` k-tiles ahead: prologue A0 B0 A1 B1 .. (A(e) for e < da, B(e)
-// for e < PF, interleaved), then per k-tile after its wait A(it + da) (< KT1), B(it + PF) (< NT, when weights stream)
+// for e < PF, interleaved), then per k-tile after its wait A(it + da) (< KT1), B(it + PF) (< NT)
 constexpr int younger_than_a_da(int T, int KT1, int NT, int PF, int da, int nb, int na) {
   int n = 0;
   bool after = false;
@@ -95,24 +101,6 @@ constexpr int younger_than_a_da(int T, int KT1, int NT, int PF, int da, int nb, 
   return n;
 }
 
-// IW: image width = height, RO: output image rows per workgroup (IW % RO == 0, IW / RO == 2),
-// CIN: block input/output channels, CMID: bottleneck width (256: one 256-wide phase per conv);
-// PF: weight prefetch distance in k-tiles; ABL (diagnostics, tools/block_ab.py): bit 0 no MFMA,
-// bit 1 no weight streaming (the prologue's fragments reused), bit 2 no A fragment reads; bit 3
-// non-temporal input / residual loads, bit 4 non-temporal output stores (both measured slower:
-// 65.6 -> 77.9 / 101.8 us, profiles/r2_s25_block_nt.txt); bit 5 per-workgroup rotation of the waves'
-// n-blocks, bit 6 k-major fragment layout; bit 7 the co-residency variant (one LDS activation image,
-// <= 168 VGPRs: bottleneck_kernel_share)
-// bias + ReLU of one C^T accumulator (4 consecutive channels of one pixel), rounded once to bf16
-__device__ __forceinline__ sat_u32x2 relu_bf16x4(const f32x4& a, const float4& b) {
-  sat_u32x2 o;
-  bf16* ob = (bf16*)&o;
-  ob[0] = (bf16)fmaxf(a[0] + b.x, 0.f);
-  ob[1] = (bf16)fmaxf(a[1] + b.y, 0.f);
-  ob[2] = (bf16)fmaxf(a[2] + b.z, 0.f);
-  ob[3] = (bf16)fmaxf(a[3] + b.w, 0.f);
-  return o;
-}
 #ifndef SAT_C2_PF   // the half-image 3x3 kernel's weight prefetch distance in k-tiles: 3 since its input staging
 #define SAT_C2_PF 3   // moved to LDS-DMA (227 VGPRs); step 6.294-6.317 -> 6.273 ms, 4: 6.287-6.293 (profiles/r5_s38, r5_s39)
 #endif
@@ -139,7 +127,132 @@ __device__ __forceinline__ sat_u32x2 relu_bf16x4(const f32x4& a, const float4& b
 #define SAT_PAIR_STORES 1
 #endif
 
-template <int IW, int RO, int CIN, int CMID, int PF, int ABL>
+// ---- pieces every body below shares (all of them stateless; the schedule stays with the body) --------------------
+// a kernel's body between its launch timestamps
+template <typename Body>
+__device__ __forceinline__ void stamped(const SatStamps& st, Body body) {
+  const SatStampT0 t0 = sat_stamp_begin(st);
+  body();
+  sat_stamp_end(st, t0);
+}
+
+// Weight fragments of k-tile T, both 32-k halves, for the NJ consecutive 16-channel n-blocks from nb0.  In the
+// fragment layout (sat_mfma_frag_layout) block (nb, ks) of a weight of KS 32-k steps is the 1 KiB at nb * KS + ks,
+// 16 B per lane: NJ x 2 loads per wave
+template <int NJ>
+__device__ __forceinline__ void load_wfrag(const bf16* wf, int nb0, int KS, int T, int lane, bf16x8 (&dst)[2][NJ]) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+      dst[ks][j] = *(const bf16x8*)(wf + ((long)((nb0 + j) * KS + 2 * T + ks) * 64 + lane) * 8);
+}
+
+// MB x NJ MFMAs of one 32-k step at raised priority: acc[i][j] += W(n-block j) . X(m-block i)^T
+template <int MB, int NJ, int MA>
+__device__ __forceinline__ void mma_step(const bf16x8 (&af)[MB], const bf16x8 (&b)[NJ], f32x4 (&acc)[MA][NJ]) {
+  static_assert(MB <= MA, "accumulators for every m-block");
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], af[i], acc[i][j], 0, 0, 0);
+}
+// One 32-deep half of a k-tile: the A fragments of m-blocks 0 .. MB-1 from LDS at base + off(i), then their MFMAs
+// (MB fragments live at once; acc may hold more m-blocks than the phase uses)
+template <int MB, int NJ, int MA, typename Off>
+__device__ __forceinline__ void mma_half(const char* base, Off off, const bf16x8 (&b)[NJ], f32x4 (&acc)[MA][NJ]) {
+  bf16x8 af[MB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i) af[i] = *(const bf16x8*)(base + off(i));
+  __builtin_amdgcn_s_setprio(1);
+  mma_step(af, b, acc);
+  __builtin_amdgcn_s_setprio(0);
+}
+// A whole 64-deep k-tile with both halves' fragments (at base + off(i, ks)) requested before the first MFMA
+template <int MB, int NJ, typename Off>
+__device__ __forceinline__ void mma_tile(const char* base, Off off, const bf16x8 (&b)[2][NJ], f32x4 (&acc)[MB][NJ]) {
+  bf16x8 af[2][MB];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int i = 0; i < MB; ++i) af[ks][i] = *(const bf16x8*)(base + off(i, ks));
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) mma_step(af[ks], b[ks], acc);
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// byte offset of the lane's A fragment (row q, 32-k half ks) in a plane image of 128-B rows whose 16-B chunk c of
+// row r sits at slot c ^ (r & 7)
+__device__ __forceinline__ int frag_off(int q, int ks, int fh) { return q * 128 + 16 * ((ks * 4 + fh) ^ (q & 7)); }
+
+// A 3x3 conv's A-fragment offsets under filter tap `tap` (row-major, (dh, dw) = (tap / 3 - 1, tap % 3 - 1)) for the
+// wave's output pixels p = p0 + 16 i (p0 includes the lane's fr).  pix(p) says where pixel p is: its image row and
+// column and the LDS row that holds it; its tap lies dh * IW + dw rows further (every form stages consecutive image
+// rows in consecutive LDS rows).  Taps in the image's padding and pixels >= npix read the zero row zr.
+struct TapPix { int y, x, row; };
+template <int IW, int MB, typename Pix>
+__device__ __forceinline__ void tap_offsets(int tap, int p0, int npix, int zr, int fh, Pix pix, int (&offs)[MB][2]) {
+  const int dh = tap / 3 - 1, dw = tap % 3 - 1;
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    const int p = p0 + i * 16;
+    const TapPix t = pix(p);
+    const bool ok = p < npix && (unsigned)(t.y + dh) < (unsigned)IW && (unsigned)(t.x + dw) < (unsigned)IW;
+    const int q = ok ? t.row + dh * IW + dw : zr;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) offs[i][ks] = frag_off(q, ks, fh);
+  }
+}
+
+// bias + ReLU of one C^T accumulator (4 consecutive channels of one pixel), rounded once to bf16
+__device__ __forceinline__ sat_u32x2 relu_bf16x4(const f32x4& a, const float4& b) {
+  sat_u32x2 o;
+  bf16* ob = (bf16*)&o;
+  ob[0] = (bf16)fmaxf(a[0] + b.x, 0.f);
+  ob[1] = (bf16)fmaxf(a[1] + b.y, 0.f);
+  ob[2] = (bf16)fmaxf(a[2] + b.z, 0.f);
+  ob[3] = (bf16)fmaxf(a[3] + b.w, 0.f);
+  return o;
+}
+
+// Global-store epilogue of a wave's MB x NJ accumulators: the lane holds channels j * 16 + 4 fh .. + 3 of row
+// i * 16 + fr, counted from the wave's first row and channel at byte off0 of an output of C channels per pixel.
+// Bias + ReLU + one rounding; even NJ: 16-B stores from n-block pairs (j, j + 1); odd NJ: from m-block pairs
+// (rows i 16 + fr and (i + 1) 16 + fr), the odd last m-block with 8-B stores.  Row r of the wave is stored when ok(r).
+template <int C, int MB, int NJ, typename Ok>
+__device__ __forceinline__ void store_relu(__amdgpu_buffer_rsrc_t rY, unsigned off0, int fr, int fh,
+                                           const f32x4 (&acc)[MB][NJ], const float4 (&bv)[NJ], Ok ok) {
+  const unsigned lane0 = off0 + (unsigned)(fr * C + 4 * fh) * 2;
+  auto at = [&](int i, int j) { return lane0 + (unsigned)(i * 16 * C + j * 16) * 2; };
+  if constexpr (NJ % 2 == 0 && SAT_PAIR_STORES) {
+#pragma unroll
+    for (int j = 0; j < NJ; j += 2)
+#pragma unroll
+      for (int i = 0; i < MB; ++i)
+        sat_st_pair16(rY, at(i, j), at(i, j) + 32, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i][j + 1], bv[j + 1]),
+                      ok(i * 16 + fr), ok(i * 16 + fr));
+  } else {
+    constexpr int MP = SAT_PAIR_STORES ? MB / 2 * 2 : 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+      for (int i = 0; i < MP; i += 2)
+        sat_st_pair16(rY, at(i, j), at(i, j) + 32 * C, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i + 1][j], bv[j]),
+                      ok(i * 16 + fr), ok((i + 1) * 16 + fr));
+#pragma unroll
+      for (int i = MP; i < MB; ++i)
+        if (ok(i * 16 + fr)) sat_st8(rY, at(i, j), relu_bf16x4(acc[i][j], bv[j]));
+    }
+  }
+}
+
+// IW: image width = height, RO: output image rows per workgroup (IW % RO == 0, IW / RO == 2),
+// CIN: block input/output channels, CMID: bottleneck width (256: one 256-wide phase per conv);
+// PF: weight prefetch distance in k-tiles.  (Measured and not kept, DESIGN.md 4.3: a 3-tile prefetch,
+// non-temporal loads / stores, rotating the waves' n-blocks per workgroup, a k-major fragment layout, one
+// shared LDS activation image.)
+template <int IW, int RO, int CIN, int CMID, int PF>
 __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
   const __amdgpu_buffer_rsrc_t rY = sat_out_rsrc(a.y, 0x7fffffffL);   // output stores (sat_common.h policy)
   static_assert(IW / RO == 2 && IW % RO == 0, "two workgroups per image");
@@ -156,39 +269,26 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
   constexpr int X1PL = X1ROWS * ROWB;            // X1 plane bytes
   constexpr int X2PL = MB2 * 16 * ROWB;          // X2 plane bytes
   constexpr int NPL = CMID / 64;
-  // SHARE (ABL bit 7, the co-residency variant): one activation image -- c2's output overwrites c1's
-  // after a barrier, and c1's input ring lives there too before c1's epilogue: 57 KB of LDS instead
-  // of 113 KB, so decoder workgroups can share the CU
-  constexpr bool SHARE = (ABL & 128) != 0;
-  constexpr int X1 = 0, X2 = SHARE ? 0 : NPL * X1PL;   // LDS regions
-  constexpr int X2P = SHARE ? X1PL : X2PL;             // X2 plane stride
-  constexpr int RING = SHARE ? 0 : X2;                 // c1 input ring
+  constexpr int X1 = 0, X2 = NPL * X1PL;         // LDS regions
+  constexpr int RING = X2;                       // c1 input ring (dead before c2's epilogue writes X2)
   constexpr int STG = 128 * ROWB;                // 128 rows x 64 channels per stage
-  static_assert(3 * STG <= NPL * (SHARE ? X1PL : X2PL), "ring fits");
-  // SHARE keeps the three folded biases in LDS (read at each epilogue) instead of 16 VGPRs
-  constexpr int SB = NPL * X1PL, NBIAS = 2 * CMID + CIN;
-  constexpr int LDS = SHARE ? SB + NBIAS * 4 : X2 + NPL * X2PL;
+  static_assert(3 * STG <= NPL * X2PL, "ring fits");
+  constexpr int LDS = X2 + NPL * X2PL;
   constexpr int KT1 = CIN / 64, KT2 = 9 * CMID / 64, NCK = CIN / 256, KT3C = CMID / 64;
   constexpr int NT = KT1 + KT2 + NCK * KT3C;
   constexpr int KS1 = CIN / 32, KS2 = 9 * CMID / 32, KS3 = CMID / 32;
   __shared__ __attribute__((aligned(16))) char smem[LDS];
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // the wave's 32 channels of each phase: n-blocks 2w, 2w+1
   const int fr = lane & 15, fh = lane >> 4;
-  // the wave's 32 output channels of each phase: n-blocks 2wn, 2wn+1 (wn rotated per workgroup in the
-  // bit-5 experiment so the workgroups of one XCD do not request the same weight lines together)
-  const int wn = (ABL & 32) ? __builtin_amdgcn_readfirstlane((w + (blockIdx.x >> 3)) & 7) : w;
   const int img = blockIdx.x >> 1, half = blockIdx.x & 1;
   const int y0 = half * RO;                      // first output image row
   const int ws = half ? IH - R1 : 0;             // first c1 image row
   const long pix_img = (long)img * IH * IW;
 
-  // ---- zero row of every X1 plane (taps in the padding read it; SHARE: written after the ring's use) ----
-  auto zero_row = [&]() {
-    if (tid < NPL * 8) *(uint4*)(smem + X1 + (tid >> 3) * X1PL + P1 * ROWB + (tid & 7) * 16) = make_uint4(0, 0, 0, 0);
-  };
-  if constexpr (!SHARE) zero_row();
+  // ---- zero row of every X1 plane (taps in the padding read it) ----
+  if (tid < NPL * 8) *(uint4*)(smem + X1 + (tid >> 3) * X1PL + P1 * ROWB + (tid & 7) * 16) = make_uint4(0, 0, 0, 0);
 
   // ---- c1 input ring: k-tile t = channels 64t.., 128 rows (rows >= P1 read zeros) ----
   const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, (int)a.x_bytes, 0x00020000);
@@ -202,46 +302,29 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
     char* st = smem + RING + (t % 3) * STG;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      // (open-coded for the ablation's cache-policy operand; otherwise sat_bdma16)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (sat_lds_void*)(st + (w * 2 + u) * 1024), 16,
-                                               dsrc[u] == kSatOOB ? (int)kSatOOB : (int)(dsrc[u] + t * 128), 0, 0,
-                                               (ABL & 8) ? 2 : 0);
+      sat_bdma16(rX, st + (w * 2 + u) * 1024, dsrc[u] == kSatOOB ? kSatOOB : dsrc[u] + t * 128);
   };
 
   // ---- weight fragments: tile T of the 68-tile schedule, this wave's n-blocks, both 32-k halves ----
   bf16x8 bq[PF + 1][2][2];
   auto load_b = [&](int T, bf16x8 (&dst)[2][2]) {
-    const bf16* base;
-    int nb0, ks0, KS, NBW;
-    if (T < KT1) { base = a.w1; nb0 = 0; ks0 = 2 * T; KS = KS1; NBW = CMID / 16; }
-    else if (T < KT1 + KT2) { base = a.w2; nb0 = 0; ks0 = 2 * (T - KT1); KS = KS2; NBW = CMID / 16; }
-    else { const int t = T - KT1 - KT2; base = a.w3; nb0 = (t / KT3C) * 16; ks0 = 2 * (t % KT3C); KS = KS3; NBW = CIN / 16; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        dst[ks][j] = (ABL & 64)   // k-major fragment layout: block (nb, ks) at ks * NB + nb
-                         ? *(const bf16x8*)(base + ((long)((ks0 + ks) * NBW + nb0 + wn * 2 + j) * 64 + lane) * 8)
-                         : *(const bf16x8*)(base + ((long)((nb0 + wn * 2 + j) * KS + ks0 + ks) * 64 + lane) * 8);
+    if (T < KT1) load_wfrag(a.w1, w * 2, KS1, T, lane, dst);
+    else if (T < KT1 + KT2) load_wfrag(a.w2, w * 2, KS2, T - KT1, lane, dst);
+    else load_wfrag(a.w3, (T - KT1 - KT2) / KT3C * 16 + w * 2, KS3, (T - KT1 - KT2) % KT3C, lane, dst);
   };
 
   // ---- A fragment offsets: row i*16 + fr of a 128-B-row image = i * 2048 (immediate) + per-lane part ----
   int offu[2];   // unshifted rows (c1 ring, X2)
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks) offu[ks] = fr * ROWB + 16 * ((ks * 4 + fh) ^ (fr & 7));
+  for (int ks = 0; ks < 2; ++ks) offu[ks] = frag_off(fr, ks, fh);
+  auto off_u = [&](int i, int ks) { return i * 16 * ROWB + offu[ks]; };
   // c2: output pixel p = i*16 + fr reads X1 row p + (y0 - ws) * IW + dh * IW + dw under tap (dh, dw),
   // or the zero row P1 where the tap falls into the image padding (or p >= PO)
   int offs[MB][2];
-  auto tap_offsets = [&](int tap) {
-    const int dh = tap / 3 - 1, dw = tap % 3 - 1;
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-      const int p = i * 16 + fr, py = p / IW, pxx = p - py * IW;
-      const bool ok = p < PO && (unsigned)(y0 + py + dh) < (unsigned)IH && (unsigned)(pxx + dw) < (unsigned)IW;
-      const int q = ok ? p + (y0 - ws + dh) * IW + dw : P1;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) offs[i][ks] = q * ROWB + 16 * ((ks * 4 + fh) ^ (q & 7));
-    }
+  auto off_s = [&](int i, int ks) { return offs[i][ks]; };
+  auto x1_pix = [&](int p) {
+    const int py = p / IW;
+    return TapPix{y0 + py, p - py * IW, p + (y0 - ws) * IW};
   };
 
   f32x4 acc[MB][2];
@@ -251,113 +334,30 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
-  // fragments + MFMAs of one 64-deep k-tile; A row block i at base + i * 16 * ROWB + offu (unshifted)
-  // or base + offs[i] (c2's shifted rows)
-  auto mma = [&](const bf16x8 (&af)[2][MB], const bf16x8 (&b)[2][2]) {
-    if constexpr (ABL & 1) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int i = 0; i < MB; ++i) asm volatile("" ::"v"(af[ks][i]));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(b[ks][j]));
-      }
-      return;
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // SHARE: one 32-deep half's fragments at a time (28 instead of 56 VGPRs)
-  auto mma_half = [&](int ks, const bf16x8 (&af)[MB], const bf16x8 (&b)[2][2]) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][j], af[i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto tile_u = [&](const char* base, const bf16x8 (&b)[2][2]) {
-    if constexpr (SHARE) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 af[MB];
-#pragma unroll
-        for (int i = 0; i < MB; ++i) af[i] = *(const bf16x8*)(base + i * 16 * ROWB + offu[ks]);
-        mma_half(ks, af, b);
-      }
-      return;
-    }
-    bf16x8 af[2][MB];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-        af[ks][i] = (ABL & 4) ? b[ks][i & 1] : *(const bf16x8*)(base + i * 16 * ROWB + offu[ks]);
-    mma(af, b);
-  };
-  auto tile_s = [&](const char* base, const bf16x8 (&b)[2][2]) {
-    if constexpr (SHARE) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 af[MB];
-#pragma unroll
-        for (int i = 0; i < MB; ++i) af[i] = *(const bf16x8*)(base + offs[i][ks]);
-        mma_half(ks, af, b);
-      }
-      return;
-    }
-    bf16x8 af[2][MB];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < MB; ++i) af[ks][i] = (ABL & 4) ? b[ks][i & 1] : *(const bf16x8*)(base + offs[i][ks]);
-    mma(af, b);
-  };
-  // epilogue into an LDS plane image: lane holds channels w*32 + j*16 + 4fh .. +3 of pixel i*16 + fr
   // bias values of the lane's channels, loaded well before their epilogue (a load issued at the
   // epilogue would be younger than the weight prefetches and drain them)
   auto load_bias = [&](const float* bias, int ch0, float4 (&bv)[2]) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) bv[j] = *(const float4*)(bias + ch0 + wn * 32 + j * 16 + 4 * fh);
+    for (int j = 0; j < 2; ++j) bv[j] = *(const float4*)(bias + ch0 + w * 32 + j * 16 + 4 * fh);
   };
-  auto lds_bias = [&](int ch0, float4 (&bv)[2]) {   // SHARE: bias values from the LDS copy
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bv[j] = *(const float4*)(smem + SB + 4 * (ch0 + wn * 32 + j * 16 + 4 * fh));
-  };
+  // epilogue into an LDS plane image: lane holds channels w*32 + j*16 + 4fh .. +3 of pixel i*16 + fr
   auto store_planes = [&](int region, int plane_bytes, const float4 (&bias)[2]) {
-    const int plane = wn >> 1;
+    const int plane = w >> 1;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const float4 bv = bias[j];
-      const int c = (wn & 1) * 4 + j * 2 + (fh >> 1);
+      const int c = (w & 1) * 4 + j * 2 + (fh >> 1);
 #pragma unroll
       for (int i = 0; i < MB; ++i) {
         const int r = i * 16 + fr;
-        sat_u32x2 o;
-        bf16* ob = (bf16*)&o;
-        ob[0] = (bf16)fmaxf(acc[i][j][0] + bv.x, 0.f);
-        ob[1] = (bf16)fmaxf(acc[i][j][1] + bv.y, 0.f);
-        ob[2] = (bf16)fmaxf(acc[i][j][2] + bv.z, 0.f);
-        ob[3] = (bf16)fmaxf(acc[i][j][3] + bv.w, 0.f);
-        *(sat_u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) = o;
+        *(sat_u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) =
+            relu_bf16x4(acc[i][j], bias[j]);
       }
     }
   };
 
   // ---- prologue ----
   float4 bias_a[2], bias_b[2];
-  if constexpr (SHARE) {   // visible after c1's first barrier
-    float* sb = (float*)(smem + SB);
-    for (int k = tid; k < NBIAS; k += 512) sb[k] = k < CMID ? a.b1[k] : (k < 2 * CMID ? a.b2[k - CMID] : a.b3[k - 2 * CMID]);
-  } else {
-    load_bias(a.b1, 0, bias_a);
-  }
+  load_bias(a.b1, 0, bias_a);
   dma_a(0);
   load_b(0, bq[0]);
   dma_a(1);
@@ -370,55 +370,45 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
     constexpr int T = decltype(Tc)::value;
     if constexpr (T < KT1) {
       // this wave's DMAs of input tile T have landed; younger: B(T), [A(T+1)], B(T+1)
-      sat_vm_lds_barrier<younger_than_a(T, KT1, NT, PF, !(ABL & 2))>();
+      sat_vm_lds_barrier<younger_than_a(T, KT1, NT, PF)>();
       if constexpr (T + 2 < KT1) dma_a(T + 2);
     }
-    if constexpr (T + PF < NT && !(ABL & 2)) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
-    constexpr int BQ = (ABL & 2) ? 0 : T % (PF + 1);
+    if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
+    const bf16x8 (&b)[2][2] = bq[T % (PF + 1)];
     if constexpr (T < KT1) {
-      tile_u(smem + RING + (T % 3) * STG, bq[BQ]);
+      mma_tile(smem + RING + (T % 3) * STG, off_u, b, acc);
       if constexpr (T == KT1 - 1) {   // c1 epilogue -> X1 (the ring is read for the last time above)
-        if constexpr (SHARE) sat_lds_barrier();   // every wave's last ring reads retired before X1 overwrites it
-        if constexpr (SHARE) lds_bias(0, bias_a);
         store_planes(X1, X1PL, bias_a);
-        if constexpr (SHARE) zero_row();
         zero_acc();
         sat_lds_barrier();
       }
     } else if constexpr (T < KT1 + KT2) {
-      constexpr int t = T - KT1, tap = t / (CMID / 64), pl = t % (CMID / 64);
-      if constexpr (t == 0 && !SHARE) load_bias(a.b2, 0, bias_b);
-      if constexpr (pl == 0) tap_offsets(tap);
-      tile_s(smem + X1 + pl * X1PL, bq[BQ]);
+      constexpr int t = T - KT1, tap = t / NPL, pl = t % NPL;
+      if constexpr (t == 0) load_bias(a.b2, 0, bias_b);
+      if constexpr (pl == 0) tap_offsets<IW>(tap, fr, PO, P1, fh, x1_pix, offs);
+      mma_tile(smem + X1 + pl * X1PL, off_s, b, acc);
       if constexpr (t == KT2 - 1) {   // c2 epilogue -> X2
-        if constexpr (SHARE) sat_lds_barrier();   // every wave's c2 reads of X1 retired before X2 overwrites it
-        if constexpr (SHARE) lds_bias(CMID, bias_b);
-        store_planes(X2, X2P, bias_b);
+        store_planes(X2, X2PL, bias_b);
         zero_acc();
         sat_lds_barrier();
       }
     } else {
       constexpr int t = T - KT1 - KT2, ck = t / KT3C, kt = t % KT3C;
-      if constexpr (kt == (SHARE ? KT3C - 1 : 0)) {   // residual rows + bias of this chunk, for its epilogue
-        if constexpr (!SHARE) load_bias(a.b3, ck * 256, bias_a);
+      if constexpr (kt == 0) {   // residual rows + bias of this chunk, for its epilogue
+        load_bias(a.b3, ck * 256, bias_a);
 #pragma unroll
         for (int i = 0; i < MB; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {   // rows past PO load a valid row (never stored): no branch
-            const int p = min(i * 16 + fr, PO - 1), ch = ck * 256 + wn * 32 + j * 16 + 4 * fh;
-            const sat_u32x2* rp = (const sat_u32x2*)(a.x + (pix_img + (long)y0 * IW + p) * CIN + ch);
-            if constexpr (ABL & 8) resv[i][j] = __builtin_nontemporal_load(rp);
-            else resv[i][j] = *rp;
+            const int p = min(i * 16 + fr, PO - 1), ch = ck * 256 + w * 32 + j * 16 + 4 * fh;
+            resv[i][j] = *(const sat_u32x2*)(a.x + (pix_img + (long)y0 * IW + p) * CIN + ch);
           }
       }
-      tile_u(smem + X2 + kt * X2P, bq[BQ]);
+      mma_tile(smem + X2 + kt * X2PL, off_u, b, acc);
       if constexpr (kt == KT3C - 1) {   // c3 epilogue: bias, fp32 residual add, ReLU, one rounding, 8-B stores
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const int ch = ck * 256 + wn * 32 + j * 16 + 4 * fh;
-          if constexpr (SHARE) {
-            if (j == 0) lds_bias(2 * CMID + ck * 256, bias_a);
-          }
+          const int ch = ck * 256 + w * 32 + j * 16 + 4 * fh;
           const float4 bv = bias_a[j];
 #pragma unroll
           for (int i = 0; i < MB; ++i) {
@@ -429,12 +419,7 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
             bf16* ob = (bf16*)&o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) ob[e] = (bf16)fmaxf(v[e] + (float)rh[e], 0.f);
-            sat_u32x2* yp = (sat_u32x2*)(a.y + (pix_img + (long)y0 * IW + p) * CIN + ch);
-            if constexpr (ABL & 16) {
-              if (p < PO) __builtin_nontemporal_store(o, yp);
-            } else {
-              if (p < PO) sat_st8(rY, (unsigned)((char*)yp - (char*)a.y), o);
-            }
+            if (p < PO) sat_st8(rY, (unsigned)(((pix_img + (long)y0 * IW + p) * CIN + ch) * 2), o);
           }
         }
         zero_acc();
@@ -443,11 +428,9 @@ __device__ __forceinline__ void bottleneck_body(const KArgs& a) {
   });
 }
 
-template <int PF, int ABL>
+template <int PF>
 __global__ __launch_bounds__(512) void bottleneck_kernel(KArgs a) {
-  const SatStampT0 t0 = sat_stamp_begin(a.st);
-  bottleneck_body<14, 7, 1024, 256, PF, ABL>(a);
-  sat_stamp_end(a.st, t0);
+  stamped(a.st, [&] { bottleneck_body<14, 7, 1024, 256, PF>(a); });
 }
 
 // The fused block for ResNet152's layer2 identity bottlenecks (28 x 28, 512 -> 128 -> 128 -> 512): one
@@ -509,63 +492,36 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
   };
 
   // ---- weight fragments of k-tile T: this wave's n-block of the phase (c3: of chunk ck), both 32-k halves ----
-  bf16x8 bq[PF + 1][2];
-  auto load_b = [&](int T, bf16x8 (&dst)[2]) {
-    const bf16* base;
-    int nb, ks0, KS;
-    if (T < KT1) { base = a.w1; nb = w; ks0 = 2 * T; KS = KS1; }
-    else if (T < KT1 + KT2) { base = a.w2; nb = w; ks0 = 2 * (T - KT1); KS = KS2; }
-    else { const int t = T - KT1 - KT2; base = a.w3; nb = (t / KT3C) * 8 + w; ks0 = 2 * (t % KT3C); KS = KS3; }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) dst[ks] = *(const bf16x8*)(base + ((long)(nb * KS + ks0 + ks) * 64 + lane) * 8);
+  bf16x8 bq[PF + 1][2][1];
+  auto load_b = [&](int T, bf16x8 (&dst)[2][1]) {
+    if (T < KT1) load_wfrag(a.w1, w, KS1, T, lane, dst);
+    else if (T < KT1 + KT2) load_wfrag(a.w2, w, KS2, T - KT1, lane, dst);
+    else load_wfrag(a.w3, (T - KT1 - KT2) / KT3C * 8 + w, KS3, (T - KT1 - KT2) % KT3C, lane, dst);
   };
 
   int offu[2];   // unshifted rows (ring, X2): row i*16 + fr at i * 16 * ROWB + offu
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks) offu[ks] = fr * ROWB + 16 * ((ks * 4 + fh) ^ (fr & 7));
+  for (int ks = 0; ks < 2; ++ks) offu[ks] = frag_off(fr, ks, fh);
   int offs[MB2][2];   // c2: output pixel p = i*16 + fr under tap (dh, dw) reads X1 slot row py + 1 + dh
-  auto tap_offsets = [&](int tap) {
-    const int dh = tap / 3 - 1, dw = tap % 3 - 1;
-#pragma unroll
-    for (int i = 0; i < MB2; ++i) {
-      const int p = i * 16 + fr, py = p / IW, pxx = p - py * IW;
-      const bool ok = p < PO && (unsigned)(y0 + py + dh) < (unsigned)IH && (unsigned)(pxx + dw) < (unsigned)IW;
-      const int q = ok ? (py + 1 + dh) * IW + pxx + dw : P1;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) offs[i][ks] = q * ROWB + 16 * ((ks * 4 + fh) ^ (q & 7));
-    }
+  auto slot_pix = [&](int p) {
+    const int py = p / IW;
+    return TapPix{y0 + py, p - py * IW, p + IW};
   };
 
-  f32x4 acc[MB1];
+  f32x4 acc[MB1][1];
   auto zero_acc = [&]() {
 #pragma unroll
-    for (int i = 0; i < MB1; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MB1; ++i) acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
   // one 64-deep k-tile over MB m-blocks, one 32-deep half at a time (MB fragments live at once)
-  auto tile_u = [&](auto MBc, const char* base, const bf16x8 (&b)[2]) {
-    constexpr int MB = decltype(MBc)::value;
+  auto tile_u = [&](auto MBc, const char* base, const bf16x8 (&b)[2][1]) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[MB];
-#pragma unroll
-      for (int i = 0; i < MB; ++i) af[i] = *(const bf16x8*)(base + i * 16 * ROWB + offu[ks]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < MB; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks], af[i], acc[i], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    for (int ks = 0; ks < 2; ++ks)
+      mma_half<decltype(MBc)::value>(base, [&](int i) { return i * 16 * ROWB + offu[ks]; }, b[ks], acc);
   };
-  auto tile_s = [&](const char* base, const bf16x8 (&b)[2]) {
+  auto tile_s = [&](const char* base, const bf16x8 (&b)[2][1]) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[MB2];
-#pragma unroll
-      for (int i = 0; i < MB2; ++i) af[i] = *(const bf16x8*)(base + offs[i][ks]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < MB2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks], af[i], acc[i], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    for (int ks = 0; ks < 2; ++ks) mma_half<MB2>(base, [&](int i) { return offs[i][ks]; }, b[ks], acc);
   };
   // epilogue into an LDS plane image: the lane holds channels 16w + 4fh .. +3 of row i*16 + fr
   auto store_planes = [&](auto MBc, int region, int plane_bytes, int rows, const float4& bv) {
@@ -574,12 +530,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
       const int r = i * 16 + fr;
-      sat_u32x2 o;
-      bf16* ob = (bf16*)&o;
-      ob[0] = (bf16)fmaxf(acc[i][0] + bv.x, 0.f);
-      ob[1] = (bf16)fmaxf(acc[i][1] + bv.y, 0.f);
-      ob[2] = (bf16)fmaxf(acc[i][2] + bv.z, 0.f);
-      ob[3] = (bf16)fmaxf(acc[i][3] + bv.w, 0.f);
+      const sat_u32x2 o = relu_bf16x4(acc[i][0], bv);
       if (r < rows) *(sat_u32x2*)(smem + region + plane * plane_bytes + r * ROWB + 16 * (c ^ (r & 7)) + 8 * (fh & 1)) = o;
     }
   };
@@ -604,11 +555,11 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
     if constexpr (T < KT1) {
       // this wave's DMAs of tile T have landed (every wave's after the barrier, which also retires every
       // wave's reads of stage (T + 2) % 3 before it is refilled)
-      sat_vm_lds_barrier<younger_than_a(T, KT1, NT, PF, true, 2, NA)>();
+      sat_vm_lds_barrier<younger_than_a(T, KT1, NT, PF, 2, NA)>();
       if constexpr (T + 2 < KT1) dma_a(T + 2);
     }
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
-    const bf16x8 (&b)[2] = bq[T % (PF + 1)];
+    const bf16x8 (&b)[2][1] = bq[T % (PF + 1)];
     if constexpr (T < KT1) {
       tile_u(std::integral_constant<int, MB1>{}, smem + RING + (T % 3) * STG, b);
       if constexpr (T == KT1 - 1) {   // c1 epilogue -> X1 (slot pixels 0 .. P1 - 1)
@@ -618,7 +569,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
       }
     } else if constexpr (T < KT1 + KT2) {
       constexpr int t = T - KT1, pl = t % NPL;
-      if constexpr (pl == 0) tap_offsets(t / NPL);
+      if constexpr (pl == 0) tap_offsets<IW>(t / NPL, fr, PO, P1, fh, slot_pix, offs);
       tile_s(smem + X1 + pl * X1PL, b);
       if constexpr (t == KT2 - 1) {   // c2 epilogue -> X2 (the ring is dead: every wave passed c1's barrier)
         store_planes(std::integral_constant<int, MB2>{}, X2, X2PL, MB2 * 16, bias2);
@@ -642,7 +593,8 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
         for (int i = 0; i < MB2; ++i) {
           const int p = i * 16 + fr;
           const bf16* rh = (const bf16*)&resv[i];
-          const float v[4] = {acc[i][0] + bias3.x, acc[i][1] + bias3.y, acc[i][2] + bias3.z, acc[i][3] + bias3.w};
+          const f32x4& c = acc[i][0];
+          const float v[4] = {c[0] + bias3.x, c[1] + bias3.y, c[2] + bias3.z, c[3] + bias3.w};
           sat_u32x2 o;
           bf16* ob = (bf16*)&o;
 #pragma unroll
@@ -656,9 +608,7 @@ __device__ __forceinline__ void block_band_body(const KArgs& a) {
 }
 
 __global__ __launch_bounds__(512) void block_band_kernel(KArgs a) {
-  const SatStampT0 t0 = sat_stamp_begin(a.st);
-  block_band_body<28, 7, 512, 128, 2>(a);
-  sat_stamp_end(a.st, t0);
+  stamped(a.st, [&] { block_band_body<28, 7, 512, 128, 2>(a); });
 }
 
 // The bottleneck's c2 phase as a conv of its own (the layer3 blocks the trunk leaves unfused, so the
@@ -720,20 +670,15 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
   for (int j = 0; j < 2; ++j) bv[j] = *(const float4*)(bias + wc * 32 + j * 16 + 4 * fh);
 
   bf16x8 bq[PF + 1][2][2];
-  auto load_b = [&](int T, bf16x8 (&dst)[2][2]) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        dst[ks][j] = *(const bf16x8*)(wf + ((long)((wc * 2 + j) * KS + 2 * T + ks) * 64 + lane) * 8);
-  };
+  auto load_b = [&](int T, bf16x8 (&dst)[2][2]) { load_wfrag(wf, wc * 2, KS, T, lane, dst); };
   sat_static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
 #pragma unroll
   for (int pl = 1; pl < NPL; ++pl) dma_plane(pl);
   if (tid < NPL * 8) *(uint4*)(smem + (tid >> 3) * X1PL + P1 * ROWB + (tid & 7) * 16) = make_uint4(0, 0, 0, 0);
 
+  // Its own copy of tap_offsets(): through the shared one this kernel takes 237 VGPRs instead of 233.
   int offs[MB][2];
-  auto tap_offsets = [&](int tap) {
+  auto tap_offsets_x1 = [&](int tap) {
     const int dh = tap / 3 - 1, dw = tap % 3 - 1;
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
@@ -741,7 +686,7 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
       const bool ok = p < PO && (unsigned)(y0 + py + dh) < (unsigned)IH && (unsigned)(pxx + dw) < (unsigned)IW;
       const int q = ok ? p + (y0 - ws + dh) * IW + dw : P1;
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) offs[i][ks] = q * ROWB + 16 * ((ks * 4 + fh) ^ (q & 7));
+      for (int ks = 0; ks < 2; ++ks) offs[i][ks] = frag_off(q, ks, fh);
     }
   };
   f32x4 acc[MB][2];
@@ -758,7 +703,7 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
     constexpr int T = decltype(Tc)::value, pl = T % NPL;
     if constexpr (T < NPL) sat_vm_lds_barrier<PPW * (NPL - 1 - T)>();   // plane T (and the zero rows) in LDS
     if constexpr (T + PF < NT && !(ABL & 1)) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
-    if constexpr (pl == 0) tap_offsets(T / NPL);
+    if constexpr (pl == 0) tap_offsets_x1(T / NPL);
     const bf16x8 (&b)[2][2] = bq[(ABL & 1) ? T % PF : T % (PF + 1)];
     bf16x8 af[2][MB];
 #pragma unroll
@@ -782,23 +727,9 @@ __device__ __forceinline__ void conv3x3_frag_body(const bf16* __restrict__ x, co
     __builtin_amdgcn_s_setprio(0);
   });
 
-  // epilogue: the lane holds channels w*32 + j*16 + 4fh .. +3 of output pixel i*16 + fr
-  if constexpr (SAT_PAIR_STORES) {
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-      const unsigned o0 = (unsigned)(((pix_img + (long)y0 * IW + i * 16 + fr) * C + wc * 32 + 4 * fh) * 2);
-      sat_st_pair16(rY, o0, o0 + 32, relu_bf16x4(acc[i][0], bv[0]), relu_bf16x4(acc[i][1], bv[1]), i * 16 + fr < PO,
-                i * 16 + fr < PO);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-        if (i * 16 + fr < PO)
-          sat_st8(rY, (unsigned)(((pix_img + (long)y0 * IW + i * 16 + fr) * C + wc * 32 + j * 16 + 4 * fh) * 2),
-                  relu_bf16x4(acc[i][j], bv[j]));
-  }
+  // epilogue: the lane holds channels wc*32 + j*16 + 4fh .. +3 of output pixel i*16 + fr
+  store_relu<C>(rY, (unsigned)(((pix_img + (long)y0 * IW) * C + wc * 32) * 2), fr, fh, acc, bv,
+                [&](int r) { return r < PO; });
 }
 
 // The same idea for a band of RO output rows of a larger image (ResNet152 layer2's c2: 28 x 28, 128 ->
@@ -817,7 +748,7 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
   constexpr int IH = IW, NPART = IH / RO, PO = RO * IW, MBT = (PO + 15) / 16;
   constexpr int MB = (MBT + WM - 1) / WM, WN = NWV / WM;   // m-blocks per wave; NWV waves = WM m-groups x WN
   constexpr int SLOTS = RO + 2, ZR = SLOTS * IW;        // LDS pixel rows + the zero row
-  constexpr int ROWB = 128, NPL = C / 64, NJ = C / (16 * WN * NSL), CS = C / NSL;
+  constexpr int NPL = C / 64, NJ = C / (16 * WN * NSL), CS = C / NSL;
   constexpr int NT = 9 * C / 64, KS = 9 * C / 32;
   // LDS-DMA pieces of 1 KB = 8 pixel rows of one plane, the zero row included (its lanes read out of bounds: zeros)
   constexpr int NPC = ZR / 8 + 1, PPW = (NPC + NWV - 1) / NWV, XPL = NPC * 1024;
@@ -841,7 +772,6 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
   const int y0 = part * RO;
   const int cb = slice * CS;                       // first output channel of this workgroup
   const long pix_img = (long)img * IH * IW;
-  const unsigned lane_b = (unsigned)lane * 16;
 
   // Slot s holds image row y0 - 1 + s: the slots are consecutive image rows, so pixel row r of a plane is image pixel
   // (y0 - 1) IW + r.  They go HBM -> LDS by buffer_load ... lds, plane by plane (lane l of a piece fetches the chunk
@@ -866,33 +796,20 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
       sat_bdma16(rX, smem + pl * XPL + dpc[u] * 1024, dsrc[u] == kSatOOB ? kSatOOB : dsrc[u] + pl * 128);
   };
   dma_plane(0);
+  const int nb0 = cb / 16 + wn * NJ;               // this wave's first 16-channel n-block
   float4 bv[NJ];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) bv[j] = *(const float4*)(bias + cb + (wn * NJ + j) * 16 + 4 * fh);
+  for (int j = 0; j < NJ; ++j) bv[j] = *(const float4*)(bias + (nb0 + j) * 16 + 4 * fh);
   bf16x8 bq[PF + 1][2][NJ];
-  auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        dst[ks][j] = *(const bf16x8*)((const char*)wf + (size_t)((cb / 16 + wn * NJ + j) * KS + 2 * T + ks) * 1024 +
-                                      lane_b);
-  };
+  auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) { load_wfrag(wf, nb0, KS, T, lane, dst); };
   sat_static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
 #pragma unroll
   for (int pl = 1; pl < NPL; ++pl) dma_plane(pl);
 
   int offs[MB][2];
-  auto tap_offsets = [&](int tap) {
-    const int dh = tap / 3 - 1, dw = tap % 3 - 1;
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-      const int p = (wm * MB + i) * 16 + fr, py = p / IW, pxx = p - py * IW;
-      const bool ok = p < PO && (unsigned)(y0 + py + dh) < (unsigned)IH && (unsigned)(pxx + dw) < (unsigned)IW;
-      const int q = ok ? (py + 1 + dh) * IW + pxx + dw : ZR;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) offs[i][ks] = q * ROWB + 16 * ((ks * 4 + fh) ^ (q & 7));
-    }
+  auto slot_pix = [&](int p) {   // band pixel p (image row y0 + py) sits in slot row py + 1
+    const int py = p / IW;
+    return TapPix{y0 + py, p - py * IW, p + IW};
   };
   f32x4 acc[MB][NJ];
 #pragma unroll
@@ -905,49 +822,14 @@ __device__ __forceinline__ void conv3x3_band_body(const bf16* __restrict__ x, co
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (T < NPL) sat_vm_lds_barrier<PPW * (NPL - 1 - T)>();   // plane T in LDS
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
-    if constexpr (pl == 0) tap_offsets(T / NPL);
+    if constexpr (pl == 0) tap_offsets<IW>(T / NPL, wm * MB * 16 + fr, PO, ZR, fh, slot_pix, offs);
     const bf16x8 (&b)[2][NJ] = bq[T % (PF + 1)];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[MB];
-#pragma unroll
-      for (int i = 0; i < MB; ++i) af[i] = *(const bf16x8*)(smem + pl * XPL + offs[i][ks]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][j], af[i], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    for (int ks = 0; ks < 2; ++ks) mma_half<MB>(smem + pl * XPL, [&](int i) { return offs[i][ks]; }, b[ks], acc);
   });
 
-  char* y_s = (char*)(y + (pix_img + (long)y0 * IW + wm * MB * 16) * C + cb + wn * NJ * 16);
-  const unsigned row_b = (unsigned)(fr * C + 4 * fh) * 2;
-  if constexpr (NJ % 2 == 0 && SAT_PAIR_STORES) {
-#pragma unroll
-    for (int j = 0; j < NJ; j += 2)
-#pragma unroll
-      for (int i = 0; i < MB; ++i) {
-        const unsigned o0 = (unsigned)(y_s - (char*)y + (size_t)(i * 16 * C + j * 16) * 2 + row_b);
-        sat_st_pair16(rY, o0, o0 + 32, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i][j + 1], bv[j + 1]),
-                  (wm * MB + i) * 16 + fr < PO, (wm * MB + i) * 16 + fr < PO);
-      }
-  } else {   // odd NJ: m-block pairs (pixels i 16 + fr and (i + 1) 16 + fr), the odd last m-block with 8-B stores
-    constexpr int MP = SAT_PAIR_STORES ? MB / 2 * 2 : 0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-      for (int i = 0; i < MP; i += 2) {
-        const unsigned oA = (unsigned)(y_s - (char*)y + (size_t)(i * 16 * C + j * 16) * 2 + row_b);
-        sat_st_pair16(rY, oA, oA + 32 * C, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i + 1][j], bv[j]),
-                  (wm * MB + i) * 16 + fr < PO, (wm * MB + i + 1) * 16 + fr < PO);
-      }
-#pragma unroll
-      for (int i = MP; i < MB; ++i)
-        if ((wm * MB + i) * 16 + fr < PO)
-          sat_st8(rY, (unsigned)(y_s - (char*)y + (size_t)(i * 16 * C + j * 16) * 2 + row_b), relu_bf16x4(acc[i][j], bv[j]));
-    }
-  }
+  store_relu<C>(rY, (unsigned)(((pix_img + (long)y0 * IW + wm * MB * 16) * C + nb0 * 16) * 2), fr, fh, acc, bv,
+                [&](int r) { return wm * MB * 16 + r < PO; });
 }
 
 // ResNet152 layer2's c2 (28 x 28, 128 -> 128) as 7-row bands on four waves of 32 channels (NJ = 2): every A
@@ -958,9 +840,7 @@ template <int PF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3x3_band4w_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                              const float* __restrict__ bias, bf16* __restrict__ y,
                                                              int nbands, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_band_body<28, 7, 128, 1, 1, PF, 4>(x, wf, bias, y, nbands);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_band_body<28, 7, 128, 1, 1, PF, 4>(x, wf, bias, y, nbands); });
 }
 
 // VGG19 block 2's 112 x 112, 128 -> 128 conv as 2-row bands (one-row halo each side: 115 KB of LDS), every
@@ -970,9 +850,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 __global__ __launch_bounds__(512) void conv3x3_band112_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                               const float* __restrict__ bias, bf16* __restrict__ y,
                                                               int nbands, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_band_body<112, 2, 128, 1, 1, 2>(x, wf, bias, y, nbands);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_band_body<112, 2, 128, 1, 1, 2>(x, wf, bias, y, nbands); });
 }
 
 // VGG19 block 3's 56 x 56, 256 -> 256 convs (three launches) as 2-row bands: the layer3 c2 half-image geometry
@@ -981,9 +859,7 @@ __global__ __launch_bounds__(512) void conv3x3_band112_kernel(const bf16* __rest
 __global__ __launch_bounds__(512) void conv3x3_band56_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                              const float* __restrict__ bias, bf16* __restrict__ y,
                                                              int nbands, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_band_body<56, 2, 256, 1, 1, 2>(x, wf, bias, y, nbands);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_band_body<56, 2, 256, 1, 1, 2>(x, wf, bias, y, nbands); });
 }
 
 // VGG19's block-5 convs (14 x 14, 512 -> 512, four launches): half images (one-row halo each side) x four
@@ -991,9 +867,7 @@ __global__ __launch_bounds__(512) void conv3x3_band56_kernel(const bf16* __restr
 __global__ __launch_bounds__(512) void conv3x3_half512_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                               const float* __restrict__ bias, bf16* __restrict__ y,
                                                               int nbands, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_band_body<14, 7, 512, 4, 1, 2>(x, wf, bias, y, nbands);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_band_body<14, 7, 512, 4, 1, 2>(x, wf, bias, y, nbands); });
 }
 
 // The same idea for images small enough to stage whole (ResNet152 layer4's stride-1 c2: 7 x 7, 512 -> 512): a
@@ -1025,11 +899,10 @@ __device__ __forceinline__ void conv3x3_img_body(const bf16* __restrict__ x, con
   const int ngrp = (nimg + G - 1) / G;
   if (grp >= ngrp) return;   // the grid rounds the groups up to whole groups of 8
   const int img0 = grp * G, nv = min(G, nimg - img0) * PI;   // valid pixels of this group
-  const int cb = slice * CS;
-  const unsigned lane_b = (unsigned)lane * 16;
   // XCD-aware weight rotation (SAT_WROT, as the band forms): the workgroups of one slice sharing an XCD start their
   // waves on different channel groups
   const int wr = SAT_WROT ? __builtin_amdgcn_readfirstlane((w + (int)((blockIdx.x >> 3) / NSL)) & 7) : w;
+  const int nb0 = slice * CS / 16 + wr * NJ;       // this wave's first 16-channel n-block
 
   uint4 xin[PER_T];
   const uint4* xs = (const uint4*)(x + (long)img0 * PI * C);
@@ -1037,15 +910,9 @@ __device__ __forceinline__ void conv3x3_img_body(const bf16* __restrict__ x, con
   for (int u = 0; u < PER_T; ++u) xin[u] = xs[min(u * 512 + tid, nv * CPP - 1)];
   float4 bv[NJ];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) bv[j] = *(const float4*)(bias + cb + (wr * NJ + j) * 16 + 4 * fh);
+  for (int j = 0; j < NJ; ++j) bv[j] = *(const float4*)(bias + (nb0 + j) * 16 + 4 * fh);
   bf16x8 bq[PF + 1][2][NJ];
-  auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        dst[ks][j] = *(const bf16x8*)((const char*)wf + (size_t)((cb / 16 + wr * NJ + j) * KS + 2 * T + ks) * 1024 + lane_b);
-  };
+  auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) { load_wfrag(wf, nb0, KS, T, lane, dst); };
   sat_static_for<PF>([&](auto e) { load_b(decltype(e)::value, bq[decltype(e)::value]); });
 #pragma unroll
   for (int u = 0; u < PER_T; ++u) {
@@ -1056,16 +923,9 @@ __device__ __forceinline__ void conv3x3_img_body(const bf16* __restrict__ x, con
   sat_lds_barrier();
 
   int offs[MB][2];
-  auto tap_offsets = [&](int tap) {
-    const int dh = tap / 3 - 1, dw = tap % 3 - 1;
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-      const int p = i * 16 + fr, g = p / PI, qq = p - g * PI, py = qq / IW, pxx = qq - py * IW;
-      const bool ok = p < P && (unsigned)(py + dh) < (unsigned)IH && (unsigned)(pxx + dw) < (unsigned)IW;
-      const int q = ok ? p + dh * IW + dw : ZR;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) offs[i][ks] = q * ROWB + 16 * ((ks * 4 + fh) ^ (q & 7));
-    }
+  auto group_pix = [&](int p) {   // pixel p of the group: image p / PI, LDS row p
+    const int g = p / PI, qq = p - g * PI, py = qq / IW;
+    return TapPix{py, qq - py * IW, p};
   };
   f32x4 acc[MB][NJ];
 #pragma unroll
@@ -1077,58 +937,20 @@ __device__ __forceinline__ void conv3x3_img_body(const bf16* __restrict__ x, con
     constexpr int T = decltype(Tc)::value, pl = T % NPL;
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
-    if constexpr (pl == 0) tap_offsets(T / NPL);
+    if constexpr (pl == 0) tap_offsets<IW>(T / NPL, fr, P, ZR, fh, group_pix, offs);
     const bf16x8 (&b)[2][NJ] = bq[T % (PF + 1)];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[MB];
-#pragma unroll
-      for (int i = 0; i < MB; ++i) af[i] = *(const bf16x8*)(smem + pl * XPL + offs[i][ks]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][j], af[i], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    for (int ks = 0; ks < 2; ++ks) mma_half<MB>(smem + pl * XPL, [&](int i) { return offs[i][ks]; }, b[ks], acc);
   });
 
-  char* y_s = (char*)(y + (long)img0 * PI * C + cb + wr * NJ * 16);
-  const unsigned row_b = (unsigned)(fr * C + 4 * fh) * 2;
-  if constexpr (NJ % 2 == 0 && SAT_PAIR_STORES) {
-#pragma unroll
-    for (int j = 0; j < NJ; j += 2)
-#pragma unroll
-      for (int i = 0; i < MB; ++i) {
-        const unsigned o0 = (unsigned)(y_s - (char*)y + (size_t)(i * 16 * C + j * 16) * 2 + row_b);
-        sat_st_pair16(rY, o0, o0 + 32, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i][j + 1], bv[j + 1]),
-                  i * 16 + fr < nv, i * 16 + fr < nv);
-      }
-  } else {   // odd NJ: m-block pairs, the odd last m-block with 8-B stores
-    constexpr int MP = SAT_PAIR_STORES ? MB / 2 * 2 : 0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-      for (int i = 0; i < MP; i += 2) {
-        const unsigned oA = (unsigned)(y_s - (char*)y + (size_t)(i * 16 * C + j * 16) * 2 + row_b);
-        sat_st_pair16(rY, oA, oA + 32 * C, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i + 1][j], bv[j]),
-                  i * 16 + fr < nv, (i + 1) * 16 + fr < nv);
-      }
-#pragma unroll
-      for (int i = MP; i < MB; ++i)
-        if (i * 16 + fr < nv)
-          sat_st8(rY, (unsigned)(y_s - (char*)y + (size_t)(i * 16 * C + j * 16) * 2 + row_b), relu_bf16x4(acc[i][j], bv[j]));
-    }
-  }
+  store_relu<C>(rY, (unsigned)(((long)img0 * PI * C + nb0 * 16) * 2), fr, fh, acc, bv, [&](int r) { return r < nv; });
 }
 
 template <int G>
 __global__ __launch_bounds__(512) void conv3x3_img_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                           const float* __restrict__ bias, bf16* __restrict__ y,
                                                           int nimg, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_img_body<7, 512, G, 4, 2>(x, wf, bias, y, nimg);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_img_body<7, 512, G, 4, 2>(x, wf, bias, y, nimg); });
 }
 
 // ResNet152 layer3's c2 when half images alone would leave CUs idle (B <= 64 per GPU: 2B workgroups): each half image
@@ -1143,12 +965,8 @@ __global__ __launch_bounds__(512) void conv3x3_img_kernel(const bf16* __restrict
 __global__ __launch_bounds__(256) void conv3x3_slice2_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                              const float* __restrict__ bias, bf16* __restrict__ y,
                                                              int nbands, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_band_body<14, 7, 256, 2, 1, SAT_SL2_PF, 4>(x, wf, bias, y, nbands);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_band_body<14, 7, 256, 2, 1, SAT_SL2_PF, 4>(x, wf, bias, y, nbands); });
 }
-
-
 
 // The bottleneck's c1 phase as a conv of its own (the unfused layer3 blocks): y = relu(x . W^T + b) for
 // x [N][IW][IW][CI], y [N][IW][IW][CM] (1x1, CI = 1024 -> CM = 256).  One workgroup per half image: its
@@ -1196,19 +1014,13 @@ __device__ __forceinline__ void conv1x1_frag_body(const bf16* __restrict__ x, co
       sat_bdma16(rX, st + (w * 2 + u) * 1024, dsrc[u] == kSatOOB ? kSatOOB : dsrc[u] + t * 128);
   };
   bf16x8 bq[PF + 1][2][NJ];
-  auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        dst[ks][j] = *(const bf16x8*)(wf + ((long)((nb0 + j) * KS + 2 * T + ks) * 64 + lane) * 8);
-  };
+  auto load_b = [&](int T, bf16x8 (&dst)[2][NJ]) { load_wfrag(wf, nb0, KS, T, lane, dst); };
   float4 bv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) bv[j] = *(const float4*)(bias + (nb0 + j) * 16 + 4 * fh);
   int offu[2];
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks) offu[ks] = fr * ROWB + 16 * ((ks * 4 + fh) ^ (fr & 7));
+  for (int ks = 0; ks < 2; ++ks) offu[ks] = frag_off(fr, ks, fh);
   f32x4 acc[MB][NJ];
 #pragma unroll
   for (int i = 0; i < MB; ++i)
@@ -1230,75 +1042,30 @@ __device__ __forceinline__ void conv1x1_frag_body(const bf16* __restrict__ x, co
     sat_vm_lds_barrier<younger_than_a_da(T, NT, NT, PF, DA, 2 * NJ, 2)>();
     if constexpr (T + DA < NT) dma_a(T + DA);
     if constexpr (T + PF < NT) load_b(T + PF, bq[(T + PF) % (PF + 1)]);
-    const bf16x8 (&b)[2][NJ] = bq[T % (PF + 1)];
-    const char* st = smem + (T % (DA + 1)) * STG;
-    bf16x8 af[2][MB];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < MB; ++i) af[ks][i] = *(const bf16x8*)(st + i * 16 * ROWB + offu[ks]);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
+    mma_tile(smem + (T % (DA + 1)) * STG, [&](int i, int ks) { return i * 16 * ROWB + offu[ks]; }, bq[T % (PF + 1)], acc);
   });
 
-  if constexpr (NJ % 2 == 0 && SAT_PAIR_STORES) {
-#pragma unroll
-    for (int j = 0; j < NJ; j += 2)
-#pragma unroll
-      for (int i = 0; i < MB; ++i) {
-        const unsigned o0 = (unsigned)(((pix0 + i * 16 + fr) * CM + (nb0 + j) * 16 + 4 * fh) * 2);
-        sat_st_pair16(rY, o0, o0 + 32, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i][j + 1], bv[j + 1]),
-                  i * 16 + fr < PO, i * 16 + fr < PO);
-      }
-  } else {   // odd NJ: m-block pairs, the odd last m-block with 8-B stores
-    constexpr int MP = SAT_PAIR_STORES ? MB / 2 * 2 : 0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-      for (int i = 0; i < MP; i += 2) {
-        const unsigned oA = (unsigned)(((pix0 + i * 16 + fr) * CM + (nb0 + j) * 16 + 4 * fh) * 2);
-        sat_st_pair16(rY, oA, oA + 32 * CM, relu_bf16x4(acc[i][j], bv[j]), relu_bf16x4(acc[i + 1][j], bv[j]),
-                  i * 16 + fr < PO, (i + 1) * 16 + fr < PO);
-      }
-#pragma unroll
-      for (int i = MP; i < MB; ++i)
-        if (i * 16 + fr < PO)
-          sat_st8(rY, (unsigned)(((pix0 + i * 16 + fr) * CM + (nb0 + j) * 16 + 4 * fh) * 2), relu_bf16x4(acc[i][j], bv[j]));
-    }
-  }
+  store_relu<CM>(rY, (unsigned)((pix0 * CM + nb0 * 16) * 2), fr, fh, acc, bv, [&](int r) { return r < PO; });
 }
 
 __global__ __launch_bounds__(512) void conv1x1_frag_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                            const float* __restrict__ bias, bf16* __restrict__ y,
                                                            unsigned x_bytes, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv1x1_frag_body<14, 7, 1024, 256, SAT_C1_PF, 1, SAT_C1_DA>(x, wf, bias, y, x_bytes, (int)gridDim.x);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv1x1_frag_body<14, 7, 1024, 256, SAT_C1_PF, 1, SAT_C1_DA>(x, wf, bias, y, x_bytes, (int)gridDim.x); });
 }
 
 // the same with each half image as two 128-channel slices (B <= 80 per GPU, as conv3x3_slice2_kernel)
 __global__ __launch_bounds__(512) void conv1x1_frag2_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                             const float* __restrict__ bias, bf16* __restrict__ y,
                                                             unsigned x_bytes, int nhalves, SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv1x1_frag_body<14, 7, 1024, 256, 2, 2>(x, wf, bias, y, x_bytes, nhalves);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv1x1_frag_body<14, 7, 1024, 256, 2, 2>(x, wf, bias, y, x_bytes, nhalves); });
 }
-
 
 template <int PF>
 __global__ __launch_bounds__(512) void conv3x3_frag_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wf,
                                                            const float* __restrict__ bias, bf16* __restrict__ y,
                                                            SatStamps st) {
-  const SatStampT0 t0 = sat_stamp_begin(st);
-  conv3x3_frag_body<14, 7, 256, PF>(x, wf, bias, y);
-  sat_stamp_end(st, t0);
+  stamped(st, [&] { conv3x3_frag_body<14, 7, 256, PF>(x, wf, bias, y); });
 }
 
 // [N][K] bf16 -> [N/16][K/32][64 lanes][8]: lane l = (fh << 4) | fr holds row 16 nb + fr, k 32 ks + 8 fh ..
@@ -1327,6 +1094,19 @@ int sat_frag_slices(int N) {
   return 2 * N < 128 ? 2 : 1;
 }
 
+// The kernels address their input and output with 32-bit buffer offsets (the input resource, sat_out_rsrc's 2 GiB
+// cap on the output): run(n0, n) launches images n0 .. n0 + n - 1, in chunks whose larger tensor (img_bytes per
+// image) stays below 2 GiB.  Returns the first non-zero result.
+template <typename Run>
+int for_image_chunks(int N, long img_bytes, Run run) {
+  const int cap = (int)(((1L << 31) - 1) / img_bytes);
+  for (int n0 = 0; n0 < N; n0 += cap) {
+    const int rc = run(n0, N - n0 < cap ? N - n0 : cap);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int sat_mfma_frag_layout(int N, int K, const void* src, void* dst, void* stream) {
@@ -1348,36 +1128,23 @@ extern "C" int sat_bottleneck_fused(int N, int H, int W, int Cin, int Cmid, int 
                                     const float* b3, void* y, const SatPolicy* policy, void* stream) {
   SAT_REQUIRE(N > 0 && x && w1f && w2f && w3f && b1 && b2 && b3 && y && x != y);
   SAT_REQUIRE(sat_bottleneck_fused_supported(H, W, Cin, Cmid, dtype));
-  {   // 32-bit buffer offsets (the input resource, sat_out_rsrc's 2 GiB cap on the output): image chunks below 2 GiB
-    const long img = 2L * H * W * Cin;
-    const int cap = (int)(((1L << 31) - 1) / img);
-    if (N > cap) {
-      for (int n0 = 0; n0 < N; n0 += cap) {
-        const int rc = sat_bottleneck_fused(N - n0 < cap ? N - n0 : cap, H, W, Cin, Cmid, dtype,
-                                            (const char*)x + n0 * img, w1f, b1, w2f, b2, w3f, b3, (char*)y + n0 * img,
-                                            policy, stream);
-        if (rc) return rc;
-      }
-      return 0;
-    }
-  }
+  SAT_REQUIRE(sat_al16(x) && sat_al16(y) && sat_al16(w1f) && sat_al16(w2f) && sat_al16(w3f) && sat_al16(b1) &&
+              sat_al16(b2) && sat_al16(b3));
   SatPolicyScope scope(policy);
-  auto al = [](const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; };
-  SAT_REQUIRE(al(x, 16) && al(y, 16) && al(w1f, 16) && al(w2f, 16) && al(w3f, 16) && al(b1, 16) && al(b2, 16) &&
-              al(b3, 16));
-  const long x_bytes = 2L * N * H * W * Cin;
-  SAT_REQUIRE(x_bytes < (1L << 31));
-  KArgs a{};
-  a.x = (const bf16*)x; a.y = (bf16*)y;
-  a.w1 = (const bf16*)w1f; a.w2 = (const bf16*)w2f; a.w3 = (const bf16*)w3f;
-  a.b1 = b1; a.b2 = b2; a.b3 = b3;
-  a.x_bytes = (unsigned)x_bytes;
-  a.st = sat_launch_stamps();
-  if (H == 28)   // layer2: 7-row bands, four workgroups per image
-    hipLaunchKernelGGL(block_band_kernel, dim3(4 * N), dim3(512), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((bottleneck_kernel<2, 0>), dim3(2 * N), dim3(512), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  const long img = 2L * H * W * Cin;
+  return for_image_chunks(N, img, [&](int n0, int n) {
+    KArgs a{};
+    a.x = (const bf16*)((const char*)x + n0 * img); a.y = (bf16*)((char*)y + n0 * img);
+    a.w1 = (const bf16*)w1f; a.w2 = (const bf16*)w2f; a.w3 = (const bf16*)w3f;
+    a.b1 = b1; a.b2 = b2; a.b3 = b3;
+    a.x_bytes = (unsigned)(n * img);
+    a.st = sat_launch_stamps();
+    if (H == 28)   // layer2: 7-row bands, four workgroups per image
+      hipLaunchKernelGGL(block_band_kernel, dim3(4 * n), dim3(512), 0, (hipStream_t)stream, a);
+    else
+      hipLaunchKernelGGL(bottleneck_kernel<2>, dim3(2 * n), dim3(512), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int sat_conv3x3_frag_supported(int H, int W, int C, int dtype) {
@@ -1390,63 +1157,46 @@ extern "C" int sat_conv3x3_frag(int N, int H, int W, int C, int dtype, const voi
                                 void* y, const SatPolicy* policy, void* stream) {
   SAT_REQUIRE(N > 0 && x && wf && b && y && x != y);
   SAT_REQUIRE(sat_conv3x3_frag_supported(H, W, C, dtype));
-  {   // image chunks whose input and output stay below 2 GiB (32-bit buffer offsets, sat_out_rsrc's cap)
-    const long img = 2L * H * W * C;
-    const int cap = (int)(((1L << 31) - 1) / img);
-    if (N > cap) {
-      for (int n0 = 0; n0 < N; n0 += cap) {
-        const int rc = sat_conv3x3_frag(N - n0 < cap ? N - n0 : cap, H, W, C, dtype, (const char*)x + n0 * img, wf, b,
-                                        (char*)y + n0 * img, policy, stream);
-        if (rc) return rc;
-      }
-      return 0;
-    }
-  }
+  SAT_REQUIRE(sat_al16(x) && sat_al16(y) && sat_al16(wf) && sat_al16(b));
   SatPolicyScope scope(policy);
-  const SatStamps st = sat_launch_stamps();
-  auto al = [](const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; };
-  SAT_REQUIRE(al(x, 16) && al(y, 16) && al(wf, 16) && al(b, 16));
   const hipStream_t s = (hipStream_t)stream;
-  const bf16 *xp = (const bf16*)x, *wp = (const bf16*)wf;
-  bf16* yp = (bf16*)y;
-  if (H == 7) {   // layer4 c2: whole images, two per workgroup (one at B <= 64), four 128-channel slices
-    const int G = (sat_policy().conv_slices == 1 || (sat_policy().conv_slices != 2 && N > 64)) ? 2 : 1;
-    const int groups = sat_cdiv(sat_cdiv(N, G), 8) * 8 * 4;
-    if (G == 2)
-      hipLaunchKernelGGL(conv3x3_img_kernel<2>, dim3(groups), dim3(512), 0, s, xp, wp, b, yp, N, st);
-    else
-      hipLaunchKernelGGL(conv3x3_img_kernel<1>, dim3(groups), dim3(512), 0, s, xp, wp, b, yp, N, st);
-    return (int)hipGetLastError();
-  }
-  if (H == 112) {   // VGG19 block 2: 2-row bands
-    hipLaunchKernelGGL(conv3x3_band112_kernel, dim3(56 * N), dim3(512), 0, s, xp, wp, b, yp, 56 * N, st);
-    return (int)hipGetLastError();
-  }
-  if (H == 56) {   // VGG19 block 3: 2-row bands
-    hipLaunchKernelGGL(conv3x3_band56_kernel, dim3(28 * N), dim3(512), 0, s, xp, wp, b, yp, 28 * N, st);
-    return (int)hipGetLastError();
-  }
-  if (H == 14 && C == 512) {   // VGG19 block 5: half images x four 128-channel slices
-    hipLaunchKernelGGL(conv3x3_half512_kernel, dim3(sat_cdiv(2 * N, 8) * 8 * 4), dim3(512), 0, s, xp, wp, b, yp, 2 * N, st);
-    return (int)hipGetLastError();
-  }
-  if (H == 28) {   // layer2 c2: 7-row bands, four workgroups per image
-    hipLaunchKernelGGL(conv3x3_band4w_kernel<1>, dim3(4 * N), dim3(256), 0, s, xp, wp, b, yp, 4 * N, st);
-    return (int)hipGetLastError();
-  }
-  // layer3 c2: half images (two workgroups per image), or two channel slices per half image when the half
-  // images alone would leave CUs idle (SatPolicy::conv_slices)
+  const bf16* wp = (const bf16*)wf;
+  const long img = 2L * H * W * C;
+  return for_image_chunks(N, img, [&](int n0, int n) {
+    const SatStamps st = sat_launch_stamps();
+    const bf16* xp = (const bf16*)((const char*)x + n0 * img);
+    bf16* yp = (bf16*)((char*)y + n0 * img);
+    if (H == 7) {   // layer4 c2: whole images, two per workgroup (one at B <= 64), four 128-channel slices
+      const int G = (sat_policy().conv_slices == 1 || (sat_policy().conv_slices != 2 && n > 64)) ? 2 : 1;
+      const int groups = sat_cdiv(sat_cdiv(n, G), 8) * 8 * 4;
+      if (G == 2)
+        hipLaunchKernelGGL(conv3x3_img_kernel<2>, dim3(groups), dim3(512), 0, s, xp, wp, b, yp, n, st);
+      else
+        hipLaunchKernelGGL(conv3x3_img_kernel<1>, dim3(groups), dim3(512), 0, s, xp, wp, b, yp, n, st);
+    } else if (H == 112) {   // VGG19 block 2: 2-row bands
+      hipLaunchKernelGGL(conv3x3_band112_kernel, dim3(56 * n), dim3(512), 0, s, xp, wp, b, yp, 56 * n, st);
+    } else if (H == 56) {   // VGG19 block 3: 2-row bands
+      hipLaunchKernelGGL(conv3x3_band56_kernel, dim3(28 * n), dim3(512), 0, s, xp, wp, b, yp, 28 * n, st);
+    } else if (H == 14 && C == 512) {   // VGG19 block 5: half images x four 128-channel slices
+      hipLaunchKernelGGL(conv3x3_half512_kernel, dim3(sat_cdiv(2 * n, 8) * 8 * 4), dim3(512), 0, s, xp, wp, b, yp, 2 * n, st);
+    } else if (H == 28) {   // layer2 c2: 7-row bands, four workgroups per image
+      hipLaunchKernelGGL(conv3x3_band4w_kernel<1>, dim3(4 * n), dim3(256), 0, s, xp, wp, b, yp, 4 * n, st);
+    } else {
+      // layer3 c2: half images (two workgroups per image), or two channel slices per half image when the half
+      // images alone would leave CUs idle (SatPolicy::conv_slices)
 #ifdef SAT_C2_FORCE_SLICES   // diagnostics builds: layer3 c2 in the given form whatever the batch
-  const int mode = SAT_C2_FORCE_SLICES;
+      const int mode = SAT_C2_FORCE_SLICES;
 #else
-  const int mode = sat_frag_slices(N);
+      const int mode = sat_frag_slices(n);
 #endif
-  const int groups = sat_cdiv(2 * N, 8) * 8 * 2;   // whole groups of 8 half images x 2 slices
-  if (mode == 1)
-    hipLaunchKernelGGL(conv3x3_frag_kernel<SAT_C2_PF>, dim3(2 * N), dim3(512), 0, s, xp, wp, b, yp, st);
-  else
-    hipLaunchKernelGGL(conv3x3_slice2_kernel, dim3(groups), dim3(256), 0, s, xp, wp, b, yp, 2 * N, st);
-  return (int)hipGetLastError();
+      const int groups = sat_cdiv(2 * n, 8) * 8 * 2;   // whole groups of 8 half images x 2 slices
+      if (mode == 1)
+        hipLaunchKernelGGL(conv3x3_frag_kernel<SAT_C2_PF>, dim3(2 * n), dim3(512), 0, s, xp, wp, b, yp, st);
+      else
+        hipLaunchKernelGGL(conv3x3_slice2_kernel, dim3(groups), dim3(256), 0, s, xp, wp, b, yp, 2 * n, st);
+    }
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int sat_conv1x1_frag_supported(int H, int W, int Cin, int Cout, int dtype) {
@@ -1457,29 +1207,18 @@ extern "C" int sat_conv1x1_frag(int N, int H, int W, int Cin, int Cout, int dtyp
                                 const float* b, void* y, const SatPolicy* policy, void* stream) {
   SAT_REQUIRE(N > 0 && x && wf && b && y && x != y);
   SAT_REQUIRE(sat_conv1x1_frag_supported(H, W, Cin, Cout, dtype));
-  {   // image chunks whose input and output stay below 2 GiB (32-bit buffer offsets, sat_out_rsrc's cap)
-    const long img = 2L * H * W * (Cin > Cout ? Cin : Cout);
-    const int cap = (int)(((1L << 31) - 1) / img);
-    if (N > cap) {
-      for (int n0 = 0; n0 < N; n0 += cap) {
-        const int rc = sat_conv1x1_frag(N - n0 < cap ? N - n0 : cap, H, W, Cin, Cout, dtype,
-                                        (const char*)x + 2L * n0 * H * W * Cin, wf, b, (char*)y + 2L * n0 * H * W * Cout,
-                                        policy, stream);
-        if (rc) return rc;
-      }
-      return 0;
-    }
-  }
+  SAT_REQUIRE(sat_al16(x) && sat_al16(y) && sat_al16(wf) && sat_al16(b));
   SatPolicyScope scope(policy);
-  auto al = [](const void* p, int a) { return ((uintptr_t)p & (a - 1)) == 0; };
-  SAT_REQUIRE(al(x, 16) && al(y, 16) && al(wf, 16) && al(b, 16));
-  const long x_bytes = 2L * N * H * W * Cin;
-  SAT_REQUIRE(x_bytes < (1L << 31));
-  if (sat_frag_slices(N) == 1)
-    hipLaunchKernelGGL(conv1x1_frag_kernel, dim3(2 * N), dim3(512), 0, (hipStream_t)stream, (const bf16*)x,
-                       (const bf16*)wf, b, (bf16*)y, (unsigned)x_bytes, sat_launch_stamps());
-  else
-    hipLaunchKernelGGL(conv1x1_frag2_kernel, dim3(sat_cdiv(2 * N, 8) * 8 * 2), dim3(512), 0, (hipStream_t)stream,
-                       (const bf16*)x, (const bf16*)wf, b, (bf16*)y, (unsigned)x_bytes, 2 * N, sat_launch_stamps());
-  return (int)hipGetLastError();
+  const long x_img = 2L * H * W * Cin, y_img = 2L * H * W * Cout;
+  return for_image_chunks(N, x_img > y_img ? x_img : y_img, [&](int n0, int n) {
+    const bf16* xp = (const bf16*)((const char*)x + n0 * x_img);
+    bf16* yp = (bf16*)((char*)y + n0 * y_img);
+    if (sat_frag_slices(n) == 1)
+      hipLaunchKernelGGL(conv1x1_frag_kernel, dim3(2 * n), dim3(512), 0, (hipStream_t)stream, xp, (const bf16*)wf, b,
+                         yp, (unsigned)(n * x_img), sat_launch_stamps());
+    else
+      hipLaunchKernelGGL(conv1x1_frag2_kernel, dim3(sat_cdiv(2 * n, 8) * 8 * 2), dim3(512), 0, (hipStream_t)stream, xp,
+                         (const bf16*)wf, b, yp, (unsigned)(n * x_img), 2 * n, sat_launch_stamps());
+    return (int)hipGetLastError();
+  });
 }
