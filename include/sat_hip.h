@@ -660,6 +660,23 @@ int sat_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   void* param_lp, int64_t n, float beta1, float beta2, float eps,
                   float step_size, float bias_correction2_sqrt, void* stream);
 
+/* --- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, L2) ---
+ * Three launches ordered by the stream alone: the partials of every gradient range, one finalize, then the update.
+ * No atomics, no host read; every sum is fp64 in a fixed order, so the norm is identical from run to run.
+ * grad_sumsq: one 256-thread workgroup per partial; workgroup i writes partials[i], the fp64 sum of squares of its
+ *   share of g[0..n) (16-B loads where g is 16-B aligned, scalars for the head and tail), 0 where the share is empty.
+ *   g needs 4-byte, partials 8-byte alignment.
+ * grad_clip_finalize: adds partials[0..n) and writes state[0] = norm (fp32), state[1] = scale =
+ *   min(1, max_norm / (norm + 1e-6)), state[2] = 1 when the total is not finite (then scale = 0), else 0, and adds
+ *   state[2] to state[3], the count of skipped steps.  state: 4 floats on the device, zeroed once by the caller.
+ * adam_step_scaled: sat_adam_step on grad[i] * state[1] (the product rounded to fp32 first: the same bits as
+ *   sat_adam_step on pre-scaled gradients); when state[2] != 0 it leaves param, both moments and param_lp untouched. */
+int sat_grad_sumsq(const float* g, int64_t n, double* partials, int n_partials, void* stream);
+int sat_grad_clip_finalize(const double* partials, int n, float max_norm, float* state, void* stream);
+int sat_adam_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                         void* param_lp, int64_t n, float beta1, float beta2, float eps,
+                         float step_size, float bias_correction2_sqrt, const float* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

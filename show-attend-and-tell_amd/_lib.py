@@ -232,6 +232,10 @@ _SIGNATURES = [
                                 c_void_p]),
     ("sat_adam_step", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
                               c_float, c_float, c_float, c_void_p]),
+    ("sat_grad_sumsq", c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    ("sat_grad_clip_finalize", c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    ("sat_adam_step_scaled", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+                                     c_float, c_float, c_float, c_void_p, c_void_p]),
 ]
 EXPORTED = [s[0] for s in _SIGNATURES]
 

@@ -734,6 +734,123 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// ---- gradient clipping by global norm ---------------------------------------
+// sum of squares -> finalize -> scaled Adam step, ordered by the stream alone.  Squares of fp32 values are exact in
+// fp64 and every sum below is fp64 in a fixed order: the norm is reproducible bit for bit and right to the last bit
+// of fp32.  state (fp32 x 4, device): [0] norm, [1] scale, [2] 1 when the total is not finite, [3] skipped steps.
+constexpr int kSumsqLoads = 4;   // independent 16-B loads per thread and loop trip
+constexpr long kSumsqSweep = 256L * kSumsqLoads;   // 16-B vectors one workgroup takes per trip
+
+__device__ __forceinline__ double sumsq4(double acc, const float4 x) {
+  acc = fma((double)x.x, (double)x.x, acc);
+  acc = fma((double)x.y, (double)x.y, acc);
+  acc = fma((double)x.z, (double)x.z, acc);
+  return fma((double)x.w, (double)x.w, acc);
+}
+// 256 threads' values -> their sum in thread 0, in a fixed order (wave butterfly, then the 4 waves in order)
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// Workgroup b of G sums the 16-B vectors [(t*G + b) * kSumsqSweep, +kSumsqSweep) for t = 0, 1, ...; workgroup 0 also
+// takes the scalar head in front of the first aligned vector and the tail behind the last.  Every workgroup writes its
+// partial, a zero where its share is empty.
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, long n,
+                                                         double* __restrict__ partials) {
+  __shared__ double sh[4];
+  const long head0 = (long)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
+  const long head = head0 < n ? head0 : n;
+  const float4* g4 = (const float4*)(g + head);
+  const long n4 = (n - head) >> 2;
+  double acc[kSumsqLoads];
+#pragma unroll
+  for (int k = 0; k < kSumsqLoads; ++k) acc[k] = 0.0;
+  const long stride = (long)gridDim.x * kSumsqSweep;
+  for (long base = blockIdx.x * kSumsqSweep; base < n4; base += stride) {
+    const long i = base + threadIdx.x;
+    float4 x[kSumsqLoads];
+    // all loads first, unconditional (an index past the end re-reads the last vector and is zeroed afterwards), so the
+    // compiler issues them back to back and waits once
+#pragma unroll
+    for (int k = 0; k < kSumsqLoads; ++k) x[k] = g4[i + 256 * k < n4 ? i + 256 * k : n4 - 1];
+#pragma unroll
+    for (int k = 0; k < kSumsqLoads; ++k) {
+      if (i + 256 * k >= n4) x[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+      acc[k] = sumsq4(acc[k], x[k]);
+    }
+  }
+  if (blockIdx.x == 0) {
+    const long tail = head + (n4 << 2);
+    if (threadIdx.x < head) acc[0] = fma((double)g[threadIdx.x], (double)g[threadIdx.x], acc[0]);
+    if (tail + threadIdx.x < n) acc[1] = fma((double)g[tail + threadIdx.x], (double)g[tail + threadIdx.x], acc[1]);
+  }
+  const double s = block_sum_f64((acc[0] + acc[1]) + (acc[2] + acc[3]), sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// one workgroup: thread t adds partials t, t + 256, ... in index order, then the fixed block sum
+__global__ void __launch_bounds__(256) grad_clip_finalize_kernel(const double* __restrict__ partials, int n,
+                                                                 float max_norm, float* __restrict__ state) {
+  __shared__ double sh[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+  const double total = block_sum_f64(acc, sh);
+  if (threadIdx.x == 0) {
+    const bool bad = !isfinite(total);
+    const float norm = (float)sqrt(total);
+    state[0] = norm;
+    state[1] = bad ? 0.f : fminf(1.f, max_norm / (norm + 1e-6f));   // torch.nn.utils.clip_grad_norm_'s coefficient
+    state[2] = bad ? 1.f : 0.f;
+    state[3] += bad ? 1.f : 0.f;
+  }
+}
+
+// gradient * scale, rounded to fp32 on its own: contraction is off for this product, so it cannot fuse into
+// adam_elem's gi - mi and the clipped step equals adam_kernel on pre-scaled gradients bit for bit
+__device__ __forceinline__ float scaled_grad(float g, float scale) {
+#pragma clang fp contract(off)
+  return g * scale;
+}
+// adam_kernel on g * state[1]; a launch that finds state[2] set (non-finite norm) touches nothing
+__global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                   float* __restrict__ v, bf16* __restrict__ p_lp, long n, float b1, float b2,
+                                   float eps, float step_size, float bc2_sqrt, const float* __restrict__ state) {
+  if (state[2] != 0.f) return;
+  const float scale = state[1];
+  const float w1 = 1.f - b1;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) &&
+                   (((uintptr_t)p_lp & 7) == 0);
+  const long n4 = vec ? n >> 2 : 0;
+  const __amdgpu_buffer_rsrc_t rp = sat_out_rsrc(p, 4 * n), rm = sat_out_rsrc(m, 4 * n), rv = sat_out_rsrc(v, 4 * n);
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 pp = ((float4*)p)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i];
+    const float4 gg = ((const float4*)g)[i];
+    adam_elem(pp.x, scaled_grad(gg.x, scale), mm.x, vv.x, w1, b2, eps, step_size, bc2_sqrt);
+    adam_elem(pp.y, scaled_grad(gg.y, scale), mm.y, vv.y, w1, b2, eps, step_size, bc2_sqrt);
+    adam_elem(pp.z, scaled_grad(gg.z, scale), mm.z, vv.z, w1, b2, eps, step_size, bc2_sqrt);
+    adam_elem(pp.w, scaled_grad(gg.w, scale), mm.w, vv.w, w1, b2, eps, step_size, bc2_sqrt);
+    sat_st16<0>(rp, (unsigned)(i * 16), *(const uint4*)&pp);
+    sat_st16<0>(rm, (unsigned)(i * 16), *(const uint4*)&mm);
+    sat_st16<0>(rv, (unsigned)(i * 16), *(const uint4*)&vv);
+    if (p_lp) {
+      uint2 o;
+      bf16* ob = (bf16*)&o;
+      ob[0] = (bf16)pp.x; ob[1] = (bf16)pp.y; ob[2] = (bf16)pp.z; ob[3] = (bf16)pp.w;
+      ((uint2*)p_lp)[i] = o;
+    }
+  }
+  for (long i = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, scaled_grad(g[i], scale), mi, vi, w1, b2, eps, step_size, bc2_sqrt);
+    m[i] = mi; v[i] = vi; p[i] = pi;
+    if (p_lp) p_lp[i] = (bf16)pi;
+  }
+}
+
 }  // namespace
 
 // ============================ internal launchers ============================
@@ -1012,6 +1129,35 @@ extern "C" int sat_adam_step(float* param, const float* grad, float* exp_avg, fl
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream, param + i, grad + i,
                        exp_avg + i, exp_avg_sq + i, param_lp ? (bf16*)param_lp + i : nullptr, (long)m, beta1, beta2,
                        eps, step_size, bias_correction2_sqrt);
+    SAT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int sat_grad_sumsq(const float* g, int64_t n, double* partials, int n_partials, void* stream) {
+  SAT_REQUIRE(partials && n >= 0 && n_partials > 0 && (g || n == 0));
+  SAT_REQUIRE(((uintptr_t)g & 3) == 0 && ((uintptr_t)partials & 7) == 0);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_partials), dim3(256), 0, (hipStream_t)stream, g, (long)n, partials);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sat_grad_clip_finalize(const double* partials, int n, float max_norm, float* state, void* stream) {
+  SAT_REQUIRE(partials && state && n > 0 && max_norm > 0.f && max_norm < __builtin_inff());
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, max_norm,
+                     state);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sat_adam_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_lp,
+                                    int64_t n, float beta1, float beta2, float eps, float step_size,
+                                    float bias_correction2_sqrt, const float* state, void* stream) {
+  SAT_REQUIRE(param && grad && exp_avg && exp_avg_sq && state && n >= 0);
+  constexpr int64_t kChunk = 1L << 28;   // as sat_adam_step: the buffer resources take 32-bit byte offsets
+  for (int64_t i = 0; i < n; i += kChunk) {
+    const int64_t m = n - i < kChunk ? n - i : kChunk;
+    hipLaunchKernelGGL(adam_scaled_kernel, dim3(grid_for((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream, param + i,
+                       grad + i, exp_avg + i, exp_avg_sq + i, param_lp ? (bf16*)param_lp + i : nullptr, (long)m, beta1,
+                       beta2, eps, step_size, bias_correction2_sqrt, state);
     SAT_LAUNCH_CHECK();
   }
   return 0;

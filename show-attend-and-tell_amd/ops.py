@@ -636,3 +636,48 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, param_lp, beta1, beta2, eps, st
     L.check(L.lib().sat_adam_step(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), L.ptr(param_lp),
                                   param.numel(), beta1, beta2, eps, step_size, bc2_sqrt, L.stream_of(param)),
             "sat_adam_step")
+
+
+GRAD_SUMSQ_SWEEP = 4096      # fp32 elements one workgroup of sat_grad_sumsq reads per loop trip (csrc/elementwise.hip)
+GRAD_SUMSQ_MAX_PARTIALS = 1024
+
+
+def grad_sumsq_partials(n):
+    """Workgroups (= partials) ``sat_grad_sumsq`` gets for a range of ``n`` elements: one per sweep, at most
+    ``GRAD_SUMSQ_MAX_PARTIALS`` (4 workgroups per CU, 64 KiB of loads in flight on each)."""
+    return max(1, min(GRAD_SUMSQ_MAX_PARTIALS, -(-int(n) // GRAD_SUMSQ_SWEEP)))
+
+
+def grad_sumsq(grad, partials):
+    """partials[i] = the fp64 sum of squares of workgroup i's share of ``grad`` (fp32, contiguous); every element of
+    ``partials`` (float64 vector) is written."""
+    L.require_device(grad, partials)
+    if grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise TypeError("grad_sumsq: grad must be a contiguous float32 tensor")
+    if partials.dtype != torch.float64 or partials.dim() != 1 or not partials.is_contiguous() \
+            or partials.numel() < 1 or partials.device != grad.device:
+        raise TypeError("grad_sumsq: partials must be a non-empty contiguous float64 vector on grad's device")
+    L.check(L.lib().sat_grad_sumsq(L.ptr(grad), grad.numel(), L.ptr(partials), partials.numel(),
+                                   L.stream_of(grad)), "sat_grad_sumsq")
+    return partials
+
+
+def grad_clip_finalize(partials, max_norm, state):
+    """state[0:3] = (norm, scale, non-finite flag) from the fp64 ``partials`` of every range; state[3] += the flag."""
+    L.require_device(partials, state)
+    if partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < 1:
+        raise TypeError("grad_clip_finalize: partials must be a non-empty contiguous float64 vector")
+    if state.dtype != torch.float32 or not state.is_contiguous() or state.numel() != 4 \
+            or state.device != partials.device:
+        raise TypeError("grad_clip_finalize: state must be 4 contiguous float32 on the partials' device")
+    L.check(L.lib().sat_grad_clip_finalize(L.ptr(partials), partials.numel(), float(max_norm), L.ptr(state),
+                                           L.stream_of(state)), "sat_grad_clip_finalize")
+    return state
+
+
+def adam_step_scaled_(param, grad, exp_avg, exp_avg_sq, param_lp, beta1, beta2, eps, step_size, bc2_sqrt, state):
+    """``adam_step_`` on ``grad * state[1]``; a no-op when ``state[2] != 0`` (``grad_clip_finalize``'s state)."""
+    L.require_device(param, grad, exp_avg, exp_avg_sq, param_lp, state)
+    L.check(L.lib().sat_adam_step_scaled(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                         L.ptr(param_lp), param.numel(), beta1, beta2, eps, step_size, bc2_sqrt,
+                                         L.ptr(state), L.stream_of(param)), "sat_adam_step_scaled")

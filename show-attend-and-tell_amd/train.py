@@ -49,6 +49,10 @@ so it cannot be disabled, as in train.py:450), plus:
                   device by sat_amd.CiderDDevice: the references, their norms and the n-gram table are resident in HBM,
                   the token matrices never leave the device, the advantage is a device subtraction and the step has no
                   device-to-host copy; the logged reward sums live on the device and are read on --log-interval steps)
+  --clip-grad-norm C  clip the gradients of every param group (decoder and, with --fine-tune-encoder, the trainable
+                  tail) to global L2 norm C inside the Adam step, on the device (sat_amd.Adam(max_grad_norm=C): no host
+                  read in the step); a step whose norm is not finite changes nothing and is counted.  Log lines gain
+                  grad_norm and skipped_steps (one host read per --log-interval line).  Default: off; C must be > 0
   --bert-embeddings  a local [30522, 768] bert-base-uncased word-embedding table (a tensor, or a
                   state_dict holding embeddings.word_embeddings.weight / embedding.weight)
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N show-attend-and-tell_amd/train.py ...``
@@ -214,7 +218,11 @@ def parse(argv=None):
     p.add_argument("--scst-reward", choices=["cider", "bleu", "cider-device"], default="cider",
                    help="with --scst: the sentence reward (CIDEr-D over token ids | sentence BLEU-4 | the same CIDEr-D "
                         "scored on the device: no host round trip in the step)")
+    p.add_argument("--clip-grad-norm", type=float, default=None, metavar="C",
+                   help="clip the gradients to global L2 norm C inside the Adam step, on the device (default: off)")
     args = p.parse_args(argv)
+    if args.clip_grad_norm is not None and not 0.0 < args.clip_grad_norm < float("inf"):
+        p.error("--clip-grad-norm must be a finite number > 0")
     if args.scst:
         if args.tf or args.tf_prob is not None:
             p.error("--scst samples the fed tokens from the model itself: it cannot be combined with --tf or "
@@ -429,6 +437,14 @@ def cached_batches(loader, cache, encoder, device, dt, max_steps):
         yield batch_idx, feats, captions
 
 
+def clip_record(opt):
+    """grad_norm and skipped_steps of the last step for a log line (--clip-grad-norm): one host read."""
+    if opt.clip_state is None:
+        return {}
+    norm, _, _, skipped = opt.clip_state.tolist()
+    return dict(grad_norm=norm, skipped_steps=int(skipped))
+
+
 def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, log, grad_ar=None, cache=None):
     """train.py:119-192.  ``grad_ar``: a sat_amd.distributed.GradAllReduce for DP (N > 1).  ``cache``: the train
     split's FeatureCache (``loader`` then is the captions-only one)."""
@@ -454,7 +470,8 @@ def train_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, world, l
         if batch_idx % args.log_interval == 0:   # train.py:183-192
             m = meters.read()
             log(dict(epoch=epoch, batch=batch_idx, train_loss=m["loss"], train_top1_acc=m["top1"],
-                     train_top5_acc=m["top5"], train_loss_raw=m["loss_val"], train_tokens=m["count"]))
+                     train_top5_acc=m["top5"], train_loss_raw=m["loss_val"], train_tokens=m["count"],
+                     **clip_record(opt)))
     if cache is not None:
         cache.check_bad_rows()   # the one host read of the gather kernel's bad-row count per epoch
     return meters.read()["loss"] if meters.last is not None else 0.0
@@ -584,7 +601,7 @@ def scst_epoch(epoch, encoder, decoder, opt, loader, args, device, dt, log, rewa
             mean_logp = float((logp * scored).sum() / scored.sum().clamp_min(1))
             last = float(loss)
             log(dict(epoch=epoch, batch=batch_idx, train_loss=last, scst_reward_sample=sums[0] / n_logged,
-                     scst_reward_greedy=sums[1] / n_logged, scst_logp=mean_logp))
+                     scst_reward_greedy=sums[1] / n_logged, scst_logp=mean_logp, **clip_record(opt)))
     if cache is not None:
         cache.check_bad_rows()
     if on_device:
@@ -683,9 +700,10 @@ def main(argv=None):
         encoder.fuse_blocks = False
     if args.fine_tune_encoder:   # the tail's parameters as a second param group (one launch per tensor)
         opt = sat_amd.Adam([{"params": list(decoder.parameters())},
-                            {"params": encoder.tail_parameters(), "lr": args.encoder_lr}], lr=args.lr)
+                            {"params": encoder.tail_parameters(), "lr": args.encoder_lr}], lr=args.lr,
+                           max_grad_norm=args.clip_grad_norm)
     else:
-        opt = sat_amd.Adam(decoder.parameters(), lr=args.lr)
+        opt = sat_amd.Adam(decoder.parameters(), lr=args.lr, max_grad_norm=args.clip_grad_norm)
     grad_ar = sat_dist.GradAllReduce(decoder) if world > 1 else None
     sched = torch.optim.lr_scheduler.StepLR(opt, args.step_size)
     caches = {}
