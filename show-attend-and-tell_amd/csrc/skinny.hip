@@ -503,7 +503,7 @@ int sat_greedy_head_mid(const HeadMidArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// the vocabulary head's form for (B, V, E): the LDS-staged one at E = 512 (partials per 16 columns), else the skinny
+// the vocabulary head's form for (B, V, E): the LDS-staged one at E = 512 (partials per 64 columns), else the skinny
 // tile (per 32)
 static bool head_out_lds(int B, int E) { return E == HO_K && B <= 128; }
 int sat_greedy_head_blocks(int B, int V, int E) { return sat_cdiv(V, head_out_lds(B, E) ? HO_BLK : SK_COLS); }
